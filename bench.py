@@ -15,7 +15,13 @@ Workloads (BASELINE.json configs): the default is the north-star scene, the Stan
     timing barrier and the max-over-ranks reduction).
 Other workloads: --workload c2_final | c5_mixed | c1_three | c4_bunny4k | c3_bunny.
 
-Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel (k_persistent) against
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: scene set-up,
+warm-up, the timed frames, the outputs (--dump-outputs DIR: the last timed frame's framebuffer
+and segment count as DIR/<name>.npy) and the line with `value` and `ms_per_step`.  Everything
+below takes runs of its own and is measured with --full only (with --adaptive the counting
+pass runs in every case: the headline counts its recorded segments).
+
+--full: `roofline` prices the dominant kernel (k_persistent) against
 its binding resource, VALU issue: useful lane-operations per second (VALU wave-instructions
 x active lanes, per segment, from the committed rocprofv3 PMC profile of the same build and
 workload) over the MI355X vector peak.  `cpu_baseline` times the reference itself
@@ -140,10 +146,19 @@ def main():
     ap.add_argument("--min-spp", type=int, default=ADAPTIVE_MIN_SPP,
                     help="adaptive renders: samples of the first pass (the reference's 16; = spp runs the phase "
                          "kernel over exactly the fixed-spp frame's samples, an overhead experiment)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed frames also run the counting pass and the roofline, the generic-build "
+                         "and adaptive-sampling frames, the CPU baselines and the RMS check against the CPU "
+                         "(off by default: a plain run times the frames and prints the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed frame returned as DIR/<name>.npy: framebuffer.npy (H*W x 3 "
+                         "float64, linear; frames over 64 MB: a fixed seeded sample of pixels, in index order) "
+                         "and segments.npy (the frame's segment count)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines and RMS check")
     ap.add_argument("--no-adaptive-leg", action="store_true",
-                    help="skip the adaptive-sampling frames timed beside a fixed-spp line")
-    ap.add_argument("--no-generic-leg", action="store_true", help="skip the generic-build comparison frames")
+                    help="--full: skip the adaptive-sampling frames timed beside a fixed-spp line")
+    ap.add_argument("--no-generic-leg", action="store_true",
+                    help="--full: skip the generic-build comparison frames")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--dist-backend", default="gloo",
                     help="process group of the N>1 timing barrier and max/sum reductions: gloo (default; no "
@@ -249,58 +264,37 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-        r = torch.tensor([rays], dtype=torch.float64, device=red_dev)
+        r = torch.tensor([rays, stats[-1]["rays_total"]], dtype=torch.float64, device=red_dev)
         dist.all_reduce(r, op=dist.ReduceOp.SUM)
-        rays_all = float(r.item())
+        rays_all, rays_last = float(r[0].item()), float(r[1].item())
         barrier()
     else:
-        rays_all = float(rays)
+        rays_all, rays_last = float(rays), float(stats[-1]["rays_total"])
     covered = bool(not np.isnan(frame.arr).any()) if rank == 0 else None
+    if args.dump_outputs:  # before any later render overwrites the frame
+        if rank == 0:
+            dump_outputs(args.dump_outputs, frame.arr, rays_last)
+        if dist is not None:
+            dist.barrier()
 
     # counting pass (diagnostic kernel build): segments, node visits and SIMD efficiency
-    cst = step(params(rtx.RTX_FLAG_COUNT | sched_flags))
-    segs = max(1, cst["rays_total"])
-    # adaptive sampling traces some samples past a pixel's convergence and discards them: the
-    # metric counts the segments of the recorded samples only (the counting pass renders the same
-    # frame and counts them per slot; deterministic, so the timed frames recorded as many)
-    recorded = cst["rays_recorded"] * steps
-    if dist is not None:
-        r = torch.tensor([float(recorded)], dtype=torch.float64, device=red_dev)
-        dist.all_reduce(r, op=dist.ReduceOp.SUM)
-        recorded = float(r.item())
-    nodes_per_seg = cst["node_visits"] / segs
-    simd_nodes = cst["node_visits"] / (64.0 * cst["wave_node_iters"]) if cst["wave_node_iters"] else None
-    simd_prims = cst["prim_tests"] / (64.0 * cst["wave_prim_iters"]) if cst["wave_prim_iters"] else None
-    prims_per_seg = cst["prim_tests"] / segs
-    boxes_per_visit = 1 if args.precision == "parity" else cst["node_bytes"] // 32
-    tris_per_seg, sphs_per_seg = cst["tri_tests"] / segs, cst["sphere_tests"] / segs
-    rects_per_seg = max(0.0, prims_per_seg - tris_per_seg - sphs_per_seg)
-    # SURVEY.md §8(d) byte model: B_seg = 32*n_box + 48*n_tri + 16*n_sph + 32*n_rect + 96.  The
-    # scene is L2/MALL-resident, so these are bytes touched in cache, not HBM traffic.
-    bytes_per_seg = (32 * boxes_per_visit * nodes_per_seg + 48 * tris_per_seg + 16 * sphs_per_seg
-                     + 32 * rects_per_seg + 96)
-    segs_per_launch = rays / max(1, hot_launches)
-    avg_launch_s = hot_ms / 1e3 / max(1, hot_launches)
-
-    roofline = valu_roofline(workload, args, segs_per_launch, avg_launch_s)
-    roofline.update({
-        "kernel": "k_persistent" if args.mode == "persistent" else "k_wf_extend",
-        "avg_launch_ms": avg_launch_s * 1e3, "segments_per_launch": segs_per_launch,
-        "bytes_touched": {"per_segment": bytes_per_seg, "GB_s": bytes_per_seg * segs_per_launch / avg_launch_s / 1e9,
-                          "l2_frac": bytes_per_seg * segs_per_launch / avg_launch_s / 1e9 / L2_SHARED_GBS,
-                          "note": "SURVEY 8(d) algorithmic bytes (nodes/primitives/path state) per segment; "
-                                  "served from L2/MALL (the scene is cache-resident), not an HBM figure; l2_frac "
-                                  "against the L2's shared-row rate, 16.8-18.8 TB/s chip-wide "
-                                  "(MI355X_MICROARCH.md, indexed rows gathered from the XCD's L2; the top)"},
-        "nodes_per_segment": nodes_per_seg, "prims_per_segment": prims_per_seg, "boxes_per_visit": boxes_per_visit,
-        "simd_efficiency_nodes": simd_nodes, "simd_efficiency_prims": simd_prims,
-        "wave_rounds_idle_frac": cst["wave_rounds_idle"] / cst["wave_rounds"] if cst["wave_rounds"] else None,
-        "lane_occupancy": (cst["wave_lanes_live"] / (64.0 * (cst["wave_rounds"] - cst["wave_rounds_idle"]))
-                           if cst["wave_rounds"] > cst["wave_rounds_idle"] else None),
-    })
+    cst = recorded = None
+    if args.full or args.adaptive:
+        cst = step(params(rtx.RTX_FLAG_COUNT | sched_flags))
+        # adaptive sampling traces some samples past a pixel's convergence and discards them: the
+        # metric counts the segments of the recorded samples only (the counting pass renders the same
+        # frame and counts them per slot; deterministic, so the timed frames recorded as many)
+        recorded = cst["rays_recorded"] * steps
+        if dist is not None:
+            r = torch.tensor([float(recorded)], dtype=torch.float64, device=red_dev)
+            dist.all_reduce(r, op=dist.ReduceOp.SUM)
+            recorded = float(r.item())
+    roofline = None
+    if args.full:
+        roofline = kernel_roofline(workload, args, cst, rays, hot_ms, hot_launches)
 
     generic_leg = None
-    if world == 1 and not args.generic and not args.no_generic_leg and args.mode == "persistent":
+    if args.full and world == 1 and not args.generic and not args.no_generic_leg and args.mode == "persistent":
         gp = params(generic=True)
         step(gp)
         g_steps = max(3, min(steps, int(1.5 / max(per_frame, 1e-4))))
@@ -315,9 +309,9 @@ def main():
                        "note": "same frame with RTX_FLAG_GENERIC: no per-scene specialisation (same pixels)"}
 
     # the reference's default sampling (adaptive, WavefrontRenderer::Render) on the same frame,
-    # timed beside the fixed-spp line so the driver's run measures it too
+    # timed beside the fixed-spp line so a --full run measures it too
     adaptive_leg = None
-    if world == 1 and not args.adaptive and not args.no_adaptive_leg and args.mode == "persistent":
+    if args.full and world == 1 and not args.adaptive and not args.no_adaptive_leg and args.mode == "persistent":
         adaptive_leg = time_adaptive(torch, step, params, per_frame, rays_all / elapsed / 1e6)
 
     out = None
@@ -347,9 +341,10 @@ def main():
                        "framebuffer": "pinned host" if frame.pinned else "pageable host (pinned staging)",
                        "frame_rows_covered": covered,
                        "parallelism": f"tile-split x{world} (interleaved {STRIPE_ROWS}-row stripes, no collectives)"},
-            "roofline": roofline,
             "rays_per_step": rays_all / steps,
         }
+        if roofline is not None:
+            out["roofline"] = roofline
         if args.adaptive:
             out["value_note"] = ("adaptive: value counts the segments of the recorded samples "
                                  "(rays_recorded, counting pass); traced_value adds the samples traced past "
@@ -360,7 +355,7 @@ def main():
             out["generic_build"] = generic_leg
         if adaptive_leg:
             out["adaptive"] = adaptive_leg
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             port, out["rms_vs_cpu"], out["rms_check"] = cpu_baseline(
                 rtx, dev, host, cam, preset, scene_name, spp, depth, args, parked, build_bits)
             # the reference itself (its own sources, oracle/_ref/ref_harness) timed here, on the
@@ -388,6 +383,59 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path, frame, rays_last):
+    """What a caller of the timed path received from the last timed frame: the linear framebuffer
+    (rtx_render_multi's out_rgb, float64) and the frame's segment count (rtx_stats.rays_total).  A
+    frame over DUMP_MAX_BYTES is cut to a fixed, seeded sample of its pixels, in index order."""
+    os.makedirs(path, exist_ok=True)
+    fb = np.asarray(frame, dtype=np.float64)
+    keep = (DUMP_MAX_BYTES - 4096) // (fb.shape[1] * 8)
+    if fb.shape[0] > keep:
+        fb = fb[np.sort(np.random.default_rng(20240607).choice(fb.shape[0], keep, replace=False))]
+    np.save(os.path.join(path, "framebuffer.npy"), np.ascontiguousarray(fb))
+    np.save(os.path.join(path, "segments.npy"), np.array([rays_last], dtype=np.float64))
+
+
+def kernel_roofline(workload, args, cst, rays, hot_ms, hot_launches):
+    """The hot kernel's roofline object: the counting pass's per-segment work beside the VALU
+    roofline of the committed PMC profile at the launch time measured over the timed frames."""
+    segs = max(1, cst["rays_total"])
+    nodes_per_seg = cst["node_visits"] / segs
+    simd_nodes = cst["node_visits"] / (64.0 * cst["wave_node_iters"]) if cst["wave_node_iters"] else None
+    simd_prims = cst["prim_tests"] / (64.0 * cst["wave_prim_iters"]) if cst["wave_prim_iters"] else None
+    prims_per_seg = cst["prim_tests"] / segs
+    boxes_per_visit = 1 if args.precision == "parity" else cst["node_bytes"] // 32
+    tris_per_seg, sphs_per_seg = cst["tri_tests"] / segs, cst["sphere_tests"] / segs
+    rects_per_seg = max(0.0, prims_per_seg - tris_per_seg - sphs_per_seg)
+    # SURVEY.md §8(d) byte model: B_seg = 32*n_box + 48*n_tri + 16*n_sph + 32*n_rect + 96.  The
+    # scene is L2/MALL-resident, so these are bytes touched in cache, not HBM traffic.
+    bytes_per_seg = (32 * boxes_per_visit * nodes_per_seg + 48 * tris_per_seg + 16 * sphs_per_seg
+                     + 32 * rects_per_seg + 96)
+    segs_per_launch = rays / max(1, hot_launches)
+    avg_launch_s = hot_ms / 1e3 / max(1, hot_launches)
+
+    roofline = valu_roofline(workload, args, segs_per_launch, avg_launch_s)
+    roofline.update({
+        "kernel": "k_persistent" if args.mode == "persistent" else "k_wf_extend",
+        "avg_launch_ms": avg_launch_s * 1e3, "segments_per_launch": segs_per_launch,
+        "bytes_touched": {"per_segment": bytes_per_seg, "GB_s": bytes_per_seg * segs_per_launch / avg_launch_s / 1e9,
+                          "l2_frac": bytes_per_seg * segs_per_launch / avg_launch_s / 1e9 / L2_SHARED_GBS,
+                          "note": "SURVEY 8(d) algorithmic bytes (nodes/primitives/path state) per segment; "
+                                  "served from L2/MALL (the scene is cache-resident), not an HBM figure; l2_frac "
+                                  "against the L2's shared-row rate, 16.8-18.8 TB/s chip-wide "
+                                  "(indexed rows gathered from the XCD's L2; the top of that range)"},
+        "nodes_per_segment": nodes_per_seg, "prims_per_segment": prims_per_seg, "boxes_per_visit": boxes_per_visit,
+        "simd_efficiency_nodes": simd_nodes, "simd_efficiency_prims": simd_prims,
+        "wave_rounds_idle_frac": cst["wave_rounds_idle"] / cst["wave_rounds"] if cst["wave_rounds"] else None,
+        "lane_occupancy": (cst["wave_lanes_live"] / (64.0 * (cst["wave_rounds"] - cst["wave_rounds_idle"]))
+                           if cst["wave_rounds"] > cst["wave_rounds_idle"] else None),
+    })
+    return roofline
 
 
 def time_adaptive(torch, step, params, per_frame_fixed, fixed_value):

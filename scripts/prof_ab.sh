@@ -14,7 +14,7 @@ for lib in "$@"; do
   if [ "$lib" = "default" ]; then L=""; else L="$R/$lib"; fi
   D="$R/gpurun_out/profab_${TAG}_$(basename "$lib" .so)"
   RTX_LIB=$L timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$D" -o run --output-format csv -- \
-    python3 "$R/bench.py" --no-cpu-baseline $ARGS > "$D.json" 2> "$D.err" || exit $?
+    python3 "$R/bench.py" --full --no-cpu-baseline $ARGS > "$D.json" 2> "$D.err" || exit $?
   python3 - "$D" "$lib" >> "$OUT" <<'PY'
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + "/*kernel_stats.csv")[0]
