@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "rtx.h"
+#include "rtx_film.h"
 #include "rtx_frame_kernels.h"
 #include "rtx_p3.h"
 #include "rtx_scan.h"
@@ -187,8 +188,29 @@ struct AdaptWs {
   }
 };
 
+// A film (rtx_film_*): its own pixel state on its scene's device; everything else a render needs
+// (radiance slots, queues, counters, the adaptive workspace) stays the scene's scratch.
+struct rtx_film {
+  rtx_scene* sc = nullptr;  // nullptr once the scene was destroyed (the film's memory went with it)
+  int device = 0;
+  rtx_camera cam{};
+  rtx_render_params prm{};  // spp unused: every rtx_film_render names its budget
+  PixelMap map{};
+  int64_t npix = 0;
+  int32_t done = 0;         // samples done: the film equals a one-shot render at spp = done
+  DevBuf sum, mean, m2, samples, conv;  // mean / m2: adaptive films only
+  mutable DevBuf stage;     // save / load: the blob's body on the device
+  PixelSoA px() const {
+    return PixelSoA{sum.as<double>(), mean.as<double>(), m2.as<double>(), samples.as<int32_t>(), conv.as<uint8_t>()};
+  }
+  void release() {
+    for (DevBuf* b : {&sum, &mean, &m2, &samples, &conv, &stage}) b->release();
+  }
+};
+
 struct rtx_scene {
   int device = 0;
+  std::vector<rtx_film*> films;  // live films of this scene (rtx_film_create / rtx_film_destroy)
   hipStream_t stream = nullptr;
   int cus = 0;
   DevBuf nodes, prims, mats, texs, images, fnodes, tri_n;
@@ -219,6 +241,10 @@ struct rtx_scene {
   double slot_mem = -1.0;  // bytes the slot buffers may take (slot_target; -1: not yet queried)
   ~rtx_scene() {
     (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+    // films outlive their scene as empty shells: their device memory goes here, and every call
+    // on them but rtx_film_destroy fails from now on
+    for (rtx_film* f : films) f->release(), f->sc = nullptr;
     aw.release();
     for (auto e : evpool) (void)hipEventDestroy(e);
     for (auto e : band_ev) (void)hipEventDestroy(e);
@@ -1233,8 +1259,17 @@ int64_t rtx_render_pixel_count(const rtx_camera* cam, const rtx_render_params* p
   return n;
 }
 
+// Whose pixel state a render advances and from which sample.  rtx_render*: the scene's own
+// px_* buffers, started here, samples [0, spp), resolved into the caller's buffers (no FilmRun).
+// A film: its own state, holding samples [0, done) already; the render adds [done, spp) and
+// leaves the running sums in place (the film resolves on demand, k_film_resolve).
+struct FilmRun {
+  PixelSoA px;
+  int32_t done;
+};
 static int render_device_impl(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, double* d_rgb,
-                              int32_t* d_spp, rtx_stats* stats, void* stream, const BandSink* sink);
+                              int32_t* d_spp, rtx_stats* stats, void* stream, const BandSink* sink,
+                              const FilmRun* film = nullptr);
 // Whether render_device_impl hands a render's output to a BandSink: fixed-spp renders
 // (RecordSample's in-order sum or the megakernel's DefaultSampler) with samples to trace.
 static bool sum_path_of(const rtx_render_params* prm) {
@@ -1248,14 +1283,18 @@ int rtx_render_device(rtx_scene* sc, const rtx_camera* cam, const rtx_render_par
 }
 
 static int render_device_impl(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, double* d_rgb,
-                              int32_t* d_spp, rtx_stats* stats, void* stream, const BandSink* sink) {
-  if (!sc || !cam || !prm || !d_rgb) return fail(RTX_ERR_INVALID, "NULL argument");
+                              int32_t* d_spp, rtx_stats* stats, void* stream, const BandSink* sink,
+                              const FilmRun* film) {
+  if (!sc || !cam || !prm || (!d_rgb && !film)) return fail(RTX_ERR_INVALID, "NULL argument");
   if (prm->spp < 0 || prm->max_depth < 0) return fail(RTX_ERR_INVALID, "negative spp / max_depth");
   if (prm->mode < RTX_MODE_WAVEFRONT || prm->mode > RTX_MODE_MEGAKERNEL) return fail(RTX_ERR_INVALID, "bad mode");
   // MegaKernel + adaptive = AdaptiveSampler(min_spp, spp, rel_threshold): up to spp + 1 samples
   const bool mk_adaptive = prm->adaptive && prm->mode == RTX_MODE_MEGAKERNEL;
   if (mk_adaptive && prm->spp >= 0x7FFFFFFF) return fail(RTX_ERR_INVALID, "spp too large");
   const int budget = mk_adaptive ? prm->spp + 1 : prm->spp;
+  // the first sample to trace: 0, or the samples a film holds already
+  const int s_begin = film ? film->done : 0;
+  if (film && (mk_adaptive || s_begin < 0 || s_begin > budget)) return fail(RTX_ERR_INVALID, "bad film sample range");
   PixelMap map;
   std::string err;
   const int64_t npix = subset_pixels(cam, prm, map, err);
@@ -1283,7 +1322,7 @@ static int render_device_impl(rtx_scene* sc, const rtx_camera* cam, const rtx_re
   // the reference's default sampling (adaptive) on the persistent kernel: in phases
   // (render_adaptive); an explicit samples_per_group keeps uniform groups
   const bool phased = prm->mode == RTX_MODE_PERSISTENT && prm->adaptive && !mk_adaptive &&
-                      prm->samples_per_group <= 0 && budget > 0 && npix > 0;
+                      prm->samples_per_group <= 0 && budget > 0 && npix > 0 && s_begin == 0;
   // One allowance (slot_allowance) for all of a scene's slot buffers: the radiance buffer of
   // uniform groups and of the adaptive first pass (lbuf), the wavefront's path queues, the
   // adaptive phases' workspace (aw).  A render keeps the other kinds' buffers as long as they
@@ -1322,18 +1361,21 @@ static int render_device_impl(rtx_scene* sc, const rtx_camera* cam, const rtx_re
         prm->mode == RTX_MODE_WAVEFRONT
             ? slot_target(sc, 3 * sizeof(double) + 2 * (9 * sizeof(double) + 3 * sizeof(uint32_t)), 1ll << 25, other)
             : slot_target(sc, 3 * sizeof(double), 1ll << kSlotTargetLog2, other);
-    K = (int)std::max<int64_t>(1, std::min<int64_t>(budget > 0 ? budget : 1, target / std::max<int64_t>(1, npix)));
+    K = (int)std::max<int64_t>(1, std::min<int64_t>(budget > s_begin ? budget - s_begin : 1,
+                                                    target / std::max<int64_t>(1, npix)));
   }
-  K = std::max(1, std::min(K, std::max(1, budget)));
+  K = std::max(1, std::min(K, std::max(1, budget - s_begin)));
   if ((int64_t)npix * K > 0xFFFFFFFFll) return fail(RTX_ERR_INVALID, "too many slots in one group (lower samples_per_group)");
   const int64_t nslots = npix * (int64_t)K;
 
   int rc;
-  if ((rc = sc->px_sum.reserve(npix * 3 * sizeof(double)))) return rc;
-  if ((rc = sc->px_mean.reserve(npix * 3 * sizeof(double)))) return rc;
-  if ((rc = sc->px_m2.reserve(npix * 3 * sizeof(double)))) return rc;
-  if ((rc = sc->px_samples.reserve(npix * sizeof(int32_t)))) return rc;
-  if ((rc = sc->px_conv.reserve(npix))) return rc;
+  if (!film) {
+    if ((rc = sc->px_sum.reserve(npix * 3 * sizeof(double)))) return rc;
+    if ((rc = sc->px_mean.reserve(npix * 3 * sizeof(double)))) return rc;
+    if ((rc = sc->px_m2.reserve(npix * 3 * sizeof(double)))) return rc;
+    if ((rc = sc->px_samples.reserve(npix * sizeof(int32_t)))) return rc;
+    if ((rc = sc->px_conv.reserve(npix))) return rc;
+  }
   if (!phased && (rc = sc->lbuf.reserve(nslots * 3 * sizeof(double)))) return rc;
   if ((rc = sc->counters.reserve(kCounterWords * sizeof(unsigned long long)))) return rc;
   const size_t qbytes = nslots * (9 * sizeof(double) + 3 * sizeof(uint32_t));
@@ -1343,12 +1385,16 @@ static int render_device_impl(rtx_scene* sc, const rtx_camera* cam, const rtx_re
   // fixed spp (RecordSample's in-order sum, or the megakernel's DefaultSampler): only the
   // running sum and count matter, and the first group starts them (k_accumulate_sum `first`)
   const bool sum_path = sum_path_of(prm);
+  const PixelSoA px = film ? film->px
+                           : PixelSoA{sc->px_sum.as<double>(), sc->px_mean.as<double>(), sc->px_m2.as<double>(),
+                                      sc->px_samples.as<int32_t>(), sc->px_conv.as<uint8_t>()};
   {
-    const PixelSoA pz{sc->px_sum.as<double>(), sc->px_mean.as<double>(), sc->px_m2.as<double>(),
-                      sc->px_samples.as<int32_t>(), sc->px_conv.as<uint8_t>()};
-    const int64_t n = std::max<int64_t>(sum_path ? 0 : npix, kCounterWords);
-    hipLaunchKernelGGL(k_frame_init, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, pz, npix,
-                       sum_path ? 0 : 1, sc->counters.as<unsigned long long>(), kCounterWords);
+    // the counters always; the pixel state only where the render starts it (a film that holds
+    // samples keeps them)
+    const int zero_px = (sum_path || s_begin > 0) ? 0 : 1;
+    const int64_t n = std::max<int64_t>(zero_px ? npix : 0, kCounterWords);
+    hipLaunchKernelGGL(k_frame_init, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, px, npix,
+                       zero_px, sc->counters.as<unsigned long long>(), kCounterWords);
     HIPC(hipGetLastError());
     if (g_debug_host) g_t_launch = host_us();
   }
@@ -1365,8 +1411,6 @@ static int render_device_impl(rtx_scene* sc, const rtx_camera* cam, const rtx_re
   bool resolved = false;
 
   unsigned long long* cnt = sc->counters.as<unsigned long long>();
-  PixelSoA px{sc->px_sum.as<double>(), sc->px_mean.as<double>(), sc->px_m2.as<double>(), sc->px_samples.as<int32_t>(),
-              sc->px_conv.as<uint8_t>()};
   RenderArgs A;
   A.S = sc->S;
   A.cam = *cam;
@@ -1375,7 +1419,7 @@ static int render_device_impl(rtx_scene* sc, const rtx_camera* cam, const rtx_re
   A.npix = npix;
   A.max_depth = prm->max_depth;
   A.scatter_api = prm->mode == RTX_MODE_MEGAKERNEL;
-  A.conv = prm->adaptive ? sc->px_conv.as<uint8_t>() : nullptr;
+  A.conv = prm->adaptive ? px.conv : nullptr;
   A.L = sc->lbuf.as<double>();
   A.counters = cnt;
   // the lean BVH4 walk stores at most fast_need + 1 stack slots (branchless pushes); the
@@ -1462,7 +1506,7 @@ static int render_device_impl(rtx_scene* sc, const rtx_camera* cam, const rtx_re
       resolved = true;
     }
   }
-  for (int s0 = 0, Kc = 0; s0 < budget && !phased; s0 += Kc) {
+  for (int s0 = s_begin, Kc = 0; s0 < budget && !phased; s0 += Kc) {
     Kc = std::min(K, budget - s0);
     // adaptive with automatic grouping: nothing can converge before min_spp, afterwards
     // small groups limit the samples traced past a pixel's convergence point
@@ -1513,7 +1557,7 @@ static int render_device_impl(rtx_scene* sc, const rtx_camera* cam, const rtx_re
       // resolved output itself (k_resolve's arithmetic), in bands when a sink takes them.
       const bool last = s0 + Kc >= budget;
       AccOut out{nullptr, nullptr, -1, prm->spp};
-      if (last) out = AccOut{d_rgb, d_spp, prm->mode == RTX_MODE_MEGAKERNEL ? 1 : 0, prm->spp};
+      if (last && !film) out = AccOut{d_rgb, d_spp, prm->mode == RTX_MODE_MEGAKERNEL ? 1 : 0, prm->spp};
       const int nb = (last && banded) ? kBands : 1;
       const int64_t align = banded ? std::max<int64_t>(1, sink->align) : 1;
       const int64_t units = (npix + align - 1) / align;
@@ -1536,7 +1580,7 @@ static int render_device_impl(rtx_scene* sc, const rtx_camera* cam, const rtx_re
                          prm->min_spp, prm->rel_threshold);
     HIPC(hipGetLastError());
   }
-  if (!resolved) {
+  if (!resolved && !film) {
     hipLaunchKernelGGL(k_resolve, dim3(pix_blocks), dim3(kBlock), 0, s, px, npix,
                        prm->mode == RTX_MODE_MEGAKERNEL ? (mk_adaptive ? 2 : 1) : 0, prm->spp, d_rgb, d_spp);
     HIPC(hipGetLastError());
@@ -1863,6 +1907,232 @@ int rtx_render_p3(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params*
   if (spp) HIPC(hipMemcpyAsync(spp, sc->out_spp.p, npix * sizeof(int32_t), hipMemcpyDeviceToHost, sc->stream));
   HIPC(hipStreamSynchronize(sc->stream));
   *out_len = hd.size() + body;
+  return RTX_OK;
+}
+
+// ---- films: a frame rendered in steps, resolved on demand, saved and continued ----------------
+// (DESIGN.md "Film")
+namespace {
+// A film's calls need its scene alive, on the film's device.
+int film_live(const rtx_film* f) {
+  if (!f) return fail(RTX_ERR_INVALID, "film is NULL");
+  if (!f->sc) return fail(RTX_ERR_INVALID, "the film's scene was destroyed");
+  if (f->sc->device != f->device) return fail(RTX_ERR_INVALID, "the film's scene is on another device");
+  return RTX_OK;
+}
+int film_sampler(const rtx_film* f) { return f->prm.mode == RTX_MODE_MEGAKERNEL ? 1 : 0; }
+FilmHeader film_header(const rtx_film* f) {
+  FilmHeader h{};
+  std::memcpy(h.magic, kFilmMagic, sizeof h.magic);
+  h.version = kFilmVersion, h.header_bytes = kFilmHeaderBytes;
+  const PixelMap& m = f->map;
+  h.W = m.W, h.H = m.H, h.stripes = m.stripes, h.x0 = m.x0, h.y0 = m.y0, h.w = m.w, h.h = m.h;
+  if (m.stripes) h.srows = m.srows, h.sidx = m.sidx, h.scount = m.scount;
+  h.seed = f->prm.seed, h.max_depth = f->prm.max_depth, h.adaptive = f->prm.adaptive ? 1 : 0;
+  h.min_spp = f->prm.min_spp, h.sampler = film_sampler(f), h.rel_threshold = f->prm.rel_threshold;
+  h.done = f->done, h.npix = f->npix;
+  return h;
+}
+int film_pack(const rtx_film* f, int to_body, hipStream_t s) {
+  const int64_t n = 3 * f->npix;
+  if (n == 0) return RTX_OK;
+  const int adaptive = f->prm.adaptive ? 1 : 0;
+  hipLaunchKernelGGL(k_film_pack, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, f->px(),
+                     film_body_at(f->stage.p, f->npix, adaptive), f->npix, adaptive, to_body);
+  HIPC(hipGetLastError());
+  return RTX_OK;
+}
+int film_resolve_on(const rtx_film* f, double* d_rgb, int32_t* d_spp, hipStream_t s) {
+  if (f->npix == 0) return RTX_OK;
+  hipLaunchKernelGGL(k_film_resolve, dim3((unsigned)((f->npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, f->px(),
+                     f->npix, film_sampler(f), f->done, d_rgb, d_spp);
+  HIPC(hipGetLastError());
+  return RTX_OK;
+}
+}  // namespace
+
+int rtx_film_create(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, rtx_film** out) {
+  if (!sc || !cam || !prm || !out) return fail(RTX_ERR_INVALID, "NULL argument");
+  *out = nullptr;
+  if (prm->max_depth < 0) return fail(RTX_ERR_INVALID, "negative max_depth");
+  if (prm->mode < RTX_MODE_WAVEFRONT || prm->mode > RTX_MODE_MEGAKERNEL) return fail(RTX_ERR_INVALID, "bad mode");
+  // AdaptiveSampler's budget is spp + 1 samples of every unfinished pixel, decided inside one
+  // call: a prefix of it is not a smaller render
+  if (prm->adaptive && prm->mode == RTX_MODE_MEGAKERNEL)
+    return fail(RTX_ERR_INVALID, "megakernel films are fixed-spp only (AdaptiveSampler does not compose across calls)");
+  auto f = std::make_unique<rtx_film>();
+  std::string err;
+  f->npix = subset_pixels(cam, prm, f->map, err);
+  if (f->npix < 0) return fail(RTX_ERR_INVALID, err);
+  f->sc = sc, f->device = sc->device, f->cam = *cam, f->prm = *prm;
+  f->prm.spp = 0;
+  f->prm.adaptive = prm->adaptive ? 1 : 0;
+  HIPC(hipSetDevice(sc->device));
+  const size_t n = (size_t)std::max<int64_t>(1, f->npix);
+  int rc = RTX_OK;
+  struct Plan {
+    DevBuf* b;
+    size_t bytes;
+  } plan[] = {{&f->sum, n * 3 * sizeof(double)},
+              {&f->mean, f->prm.adaptive ? n * 3 * sizeof(double) : 0},
+              {&f->m2, f->prm.adaptive ? n * 3 * sizeof(double) : 0},
+              {&f->samples, n * sizeof(int32_t)},
+              {&f->conv, n}};
+  for (const Plan& q : plan) {
+    if (!q.bytes) continue;
+    if ((rc = q.b->reserve(q.bytes))) break;
+    if (hipMemsetAsync(q.b->p, 0, q.bytes, sc->stream) != hipSuccess) {
+      rc = fail(RTX_ERR_HIP, "hipMemsetAsync of the film's state failed");
+      break;
+    }
+  }
+  if (rc) {
+    f->release();
+    return rc;
+  }
+  sc->films.push_back(f.get());
+  *out = f.release();
+  return RTX_OK;
+}
+
+int rtx_film_destroy(rtx_film* f) {
+  if (!f) return RTX_OK;
+  if (f->sc) {
+    (void)hipSetDevice(f->device);
+    (void)hipStreamSynchronize(f->sc->stream);  // a render queued without stats may still write the state
+    auto& v = f->sc->films;
+    v.erase(std::remove(v.begin(), v.end(), f), v.end());
+    f->release();
+  }
+  delete f;
+  return RTX_OK;
+}
+
+int rtx_film_samples(const rtx_film* f, int32_t* done) {
+  if (!f || !done) return fail(RTX_ERR_INVALID, "NULL argument");
+  *done = f->done;
+  return RTX_OK;
+}
+
+int rtx_film_render(rtx_film* f, int32_t budget, rtx_stats* stats) {
+  int rc;
+  if ((rc = film_live(f))) return rc;
+  if (budget < 0) return fail(RTX_ERR_INVALID, "negative budget");
+  if (stats) *stats = rtx_stats{};
+  if (budget <= f->done) return RTX_OK;
+  rtx_render_params q = f->prm;
+  q.spp = budget;
+  const FilmRun run{f->px(), f->done};
+  if ((rc = render_device_impl(f->sc, &f->cam, &q, nullptr, nullptr, stats, f->sc->stream, nullptr, &run))) return rc;
+  f->done = budget;
+  return RTX_OK;
+}
+
+int rtx_film_resolve_device(rtx_film* f, double* d_rgb, int32_t* d_spp, void* stream) {
+  int rc;
+  if ((rc = film_live(f))) return rc;
+  if (!d_rgb) return fail(RTX_ERR_INVALID, "NULL argument");
+  HIPC(hipSetDevice(f->device));
+  hipStream_t s = stream ? (hipStream_t)stream : f->sc->stream;
+  if (s != f->sc->stream) HIPC(hipStreamSynchronize(f->sc->stream));  // the film's renders run on the scene's stream
+  return film_resolve_on(f, d_rgb, d_spp, s);
+}
+
+int rtx_film_resolve(rtx_film* f, double* rgb, int32_t* spp) {
+  int rc;
+  if ((rc = film_live(f))) return rc;
+  if (!rgb) return fail(RTX_ERR_INVALID, "NULL argument");
+  rtx_scene* sc = f->sc;
+  HIPC(hipSetDevice(f->device));
+  const int64_t npix = f->npix;
+  if ((rc = sc->out_rgb.reserve(std::max<int64_t>(1, npix) * 3 * sizeof(double)))) return rc;
+  if ((rc = sc->out_spp.reserve(std::max<int64_t>(1, npix) * sizeof(int32_t)))) return rc;
+  if ((rc = film_resolve_on(f, sc->out_rgb.as<double>(), sc->out_spp.as<int32_t>(), sc->stream))) return rc;
+  HIPC(hipMemcpyAsync(rgb, sc->out_rgb.p, npix * 3 * sizeof(double), hipMemcpyDeviceToHost, sc->stream));
+  if (spp) HIPC(hipMemcpyAsync(spp, sc->out_spp.p, npix * sizeof(int32_t), hipMemcpyDeviceToHost, sc->stream));
+  HIPC(hipStreamSynchronize(sc->stream));
+  return RTX_OK;
+}
+
+int rtx_film_p3(rtx_film* f, char* out, size_t cap, size_t* out_len) {
+  int rc;
+  if ((rc = film_live(f))) return rc;
+  if (!out || !out_len) return fail(RTX_ERR_INVALID, "NULL argument");
+  rtx_scene* sc = f->sc;
+  const int64_t npix = f->npix;
+  const std::string hd = p3_header(f->map.w, f->map.h);
+  if (cap < hd.size() + (size_t)npix * rtxp3::kMaxLine) return fail(RTX_ERR_INVALID, "output buffer below rtx_p3_max_bytes");
+  HIPC(hipSetDevice(f->device));
+  if ((rc = sc->out_rgb.reserve(std::max<int64_t>(1, npix) * 3 * sizeof(double)))) return rc;
+  if ((rc = film_resolve_on(f, sc->out_rgb.as<double>(), nullptr, sc->stream))) return rc;
+  size_t body = 0;
+  if ((rc = p3_encode(sc, sc->out_rgb.as<double>(), npix, &body, sc->stream))) return rc;
+  std::memcpy(out, hd.data(), hd.size());
+  HIPC(hipMemcpyAsync(out + hd.size(), sc->p3_body.p, body, hipMemcpyDeviceToHost, sc->stream));
+  HIPC(hipStreamSynchronize(sc->stream));
+  *out_len = hd.size() + body;
+  return RTX_OK;
+}
+
+size_t rtx_film_state_bytes(const rtx_film* f) {
+  if (!f) {
+    (void)fail(RTX_ERR_INVALID, "film is NULL");
+    return 0;
+  }
+  return kFilmHeaderBytes + film_body_bytes(f->npix, f->prm.adaptive);
+}
+
+int rtx_film_save(const rtx_film* f, void* blob, size_t cap, size_t* len) {
+  int rc;
+  if ((rc = film_live(f))) return rc;
+  if (!blob || !len) return fail(RTX_ERR_INVALID, "NULL argument");
+  const size_t body = film_body_bytes(f->npix, f->prm.adaptive);
+  if (cap < kFilmHeaderBytes + body) return fail(RTX_ERR_INVALID, "blob buffer below rtx_film_state_bytes");
+  HIPC(hipSetDevice(f->device));
+  hipStream_t s = f->sc->stream;
+  if ((rc = f->stage.reserve(std::max<size_t>(16, body)))) return rc;
+  if ((rc = film_pack(f, 1, s))) return rc;
+  if (body) HIPC(hipMemcpyAsync((char*)blob + kFilmHeaderBytes, f->stage.p, body, hipMemcpyDeviceToHost, s));
+  HIPC(hipStreamSynchronize(s));
+  const FilmHeader h = film_header(f);
+  std::memcpy(blob, &h, sizeof h);
+  *len = kFilmHeaderBytes + body;
+  return RTX_OK;
+}
+
+int rtx_film_blob_check(const void* blob, size_t len) {
+  const std::string e = film_blob_error(blob, len);
+  return e.empty() ? RTX_OK : fail(RTX_ERR_INVALID, "film blob: " + e);
+}
+
+int rtx_film_load(rtx_film* f, const void* blob, size_t len) {
+  int rc;
+  if ((rc = film_live(f))) return rc;
+  FilmHeader b;
+  const std::string e = film_blob_error(blob, len, &b);
+  if (!e.empty()) return fail(RTX_ERR_INVALID, "film blob: " + e);
+  // everything that decides a sample's value or a pixel's place must be the film's own
+  const FilmHeader h = film_header(f);
+  const char* field = nullptr;
+  if (b.W != h.W || b.H != h.H) field = "image size";
+  else if (b.stripes != h.stripes || b.x0 != h.x0 || b.y0 != h.y0 || b.w != h.w || b.h != h.h || b.srows != h.srows ||
+           b.sidx != h.sidx || b.scount != h.scount || b.npix != h.npix)
+    field = "pixel map";
+  else if (b.seed != h.seed) field = "seed";
+  else if (b.max_depth != h.max_depth) field = "max_depth";
+  else if (b.adaptive != h.adaptive) field = "adaptive";
+  else if (b.sampler != h.sampler) field = "sampler (wavefront family / megakernel)";
+  else if (h.adaptive && b.min_spp != h.min_spp) field = "min_spp";
+  else if (h.adaptive && std::memcmp(&b.rel_threshold, &h.rel_threshold, sizeof(double)) != 0) field = "rel_threshold";
+  if (field) return fail(RTX_ERR_INVALID, std::string("film blob: ") + field + " differs from the film's");
+  const size_t body = film_body_bytes(f->npix, h.adaptive);
+  HIPC(hipSetDevice(f->device));
+  hipStream_t s = f->sc->stream;
+  if ((rc = f->stage.reserve(std::max<size_t>(16, body)))) return rc;
+  if (body) HIPC(hipMemcpyAsync(f->stage.p, (const char*)blob + kFilmHeaderBytes, body, hipMemcpyHostToDevice, s));
+  if ((rc = film_pack(f, 0, s))) return rc;
+  HIPC(hipStreamSynchronize(s));  // the blob is the caller's memory
+  f->done = b.done;
   return RTX_OK;
 }
 

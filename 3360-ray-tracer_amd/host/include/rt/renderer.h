@@ -3,7 +3,9 @@
 #pragma once
 
 #include <cstdint>
+#include <functional>
 #include <iostream>
+#include <string>
 #include <vector>
 
 #include "rt/integrator.h"
@@ -36,6 +38,18 @@ class WavefrontRenderer {
   // same for every device count.
   void set_devices(const std::vector<int>& devices, int stripe_rows = 8);
   void set_gpus(int n);  // devices 0 .. n-1 (the integrator's device first)
+  // Render() through a film (rtx_film_*), single device only (with set_devices / set_gpus active
+  // Render() throws).  The final output is byte-identical to the plain Render() at the same
+  // max_samples.
+  //   set_progressive(n): n chunks, budgets ceil(k * max_samples / n); after each one the
+  //     preview callback (if set) gets the budget reached and the P3 bytes of the frame so far
+  //   set_checkpoint(path): the film's state is written there after the last chunk
+  //   set_resume(path): the film starts from the state saved there (same scene, camera, seed,
+  //     depth and sampling; samples already done are not traced again)
+  void set_progressive(int chunks) { chunks_ = chunks; }
+  void set_checkpoint(const std::string& path) { checkpoint_ = path; }
+  void set_resume(const std::string& path) { resume_ = path; }
+  void set_preview(std::function<void(int budget, const std::string& p3)> f) { preview_ = std::move(f); }
   void set_seed(uint64_t s) { params_.seed = s; }
   void set_adaptive(bool on) { params_.adaptive = on ? 1 : 0; }
   void set_mode(int mode) { params_.mode = mode; }
@@ -56,6 +70,10 @@ class WavefrontRenderer {
   std::vector<int> devices_;          // the frame's devices, the integrator's first (set_devices)
   std::vector<rtx_scene*> extra_;     // their device-resident copies of the scene
   int stripe_rows_ = 8;
+  int chunks_ = 0;                    // > 0: progressive (set_progressive)
+  std::string checkpoint_, resume_;
+  std::function<void(int, const std::string&)> preview_;
+  void RenderFilm(integrator::GpuRayIntegrator* gpu, const rtx_render_params& p, std::ostream& out);
 };
 
 // MegaKernel + DefaultSampler semantics (recursive GetPixel with the Scatter API, camera.h:

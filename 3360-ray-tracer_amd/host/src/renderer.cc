@@ -1,4 +1,6 @@
 // renderer.cc — GpuRayIntegrator, WavefrontRenderer and MegaKernel over the C ABI.
+#include <fstream>
+#include <iterator>
 #include <stdexcept>
 
 #include "rt/material.h"
@@ -120,6 +122,14 @@ void WavefrontRenderer::Render(std::ostream& out) {
   rgb_.assign(3 * n, 0.0);
   spp_.assign(n, 0);
   // wavefront.cc:238-241: the P3 text is formatted on the device (rtx_render_p3)
+  if (chunks_ > 0 || !checkpoint_.empty() || !resume_.empty()) {
+    if (devices_.size() > 1)
+      throw std::invalid_argument(
+          "WavefrontRenderer: set_progressive / set_checkpoint / set_resume render through one film on one device; "
+          "not with set_devices / set_gpus");
+    RenderFilm(gpu, p, out);
+    return;
+  }
   std::string bytes(rtx_p3_max_bytes(dc.image_width, dc.image_height), '\0');
   size_t len = 0;
   if (devices_.size() > 1) {  // one frame over several devices, gathered on the host
@@ -145,6 +155,60 @@ void WavefrontRenderer::Render(std::ostream& out) {
   }
   if (rtx_render_p3(gpu->device_scene(), &dc, &p, bytes.data(), bytes.size(), &len, rgb_.data(), spp_.data(), &stats_) != RTX_OK)
     throw std::runtime_error(std::string("rtx_render_p3: ") + rtx_last_error());
+  out.write(bytes.data(), (std::streamsize)len);
+}
+
+// The frame through a film: optionally from a saved state, in chunks with a preview after each,
+// the state saved at the end.  The output equals the one-shot frame's (rtx_film_render).
+void WavefrontRenderer::RenderFilm(integrator::GpuRayIntegrator* gpu, const rtx_render_params& p, std::ostream& out) {
+  const rtx_camera& dc = cam.device();
+  struct Owner {
+    rtx_film* f = nullptr;
+    ~Owner() { rtx_film_destroy(f); }
+  } film;
+  if (rtx_film_create(gpu->device_scene(), &dc, &p, &film.f) != RTX_OK)
+    throw std::runtime_error(std::string("rtx_film_create: ") + rtx_last_error());
+  if (!resume_.empty()) {
+    std::ifstream in(resume_, std::ios::binary);
+    if (!in) throw std::runtime_error("cannot read " + resume_);
+    const std::string blob((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+    if (rtx_film_load(film.f, blob.data(), blob.size()) != RTX_OK)
+      throw std::runtime_error(resume_ + ": " + rtx_last_error());
+  }
+  std::string bytes(rtx_p3_max_bytes(dc.image_width, dc.image_height), '\0');
+  size_t len = 0;
+  auto p3 = [&] {
+    if (rtx_film_p3(film.f, bytes.data(), bytes.size(), &len) != RTX_OK)
+      throw std::runtime_error(std::string("rtx_film_p3: ") + rtx_last_error());
+  };
+  const int chunks = chunks_ > 0 ? chunks_ : 1;
+  stats_ = rtx_stats{};
+  for (int k = 1; k <= chunks; k++) {
+    const int budget = (int)(((int64_t)k * p.spp + chunks - 1) / chunks);  // ceil(k spp / chunks)
+    rtx_stats st{};
+    if (rtx_film_render(film.f, budget, &st) != RTX_OK)
+      throw std::runtime_error(std::string("rtx_film_render: ") + rtx_last_error());
+    stats_.rays_primary += st.rays_primary, stats_.rays_total += st.rays_total, stats_.paths += st.paths;
+    stats_.kernel_ms += st.kernel_ms, stats_.hot_kernel_ms += st.hot_kernel_ms, stats_.hot_launches += st.hot_launches;
+    if (st.hot_launches) stats_.build = st.build, stats_.parked = st.parked, stats_.node_bytes = st.node_bytes;
+    if (preview_ && k < chunks) {
+      p3();
+      preview_(budget, bytes.substr(0, len));
+    }
+  }
+  if (rtx_film_resolve(film.f, rgb_.data(), spp_.data()) != RTX_OK)
+    throw std::runtime_error(std::string("rtx_film_resolve: ") + rtx_last_error());
+  p3();
+  if (preview_) preview_(p.spp, bytes.substr(0, len));
+  if (!checkpoint_.empty()) {
+    std::string blob(rtx_film_state_bytes(film.f), '\0');
+    size_t n = 0;
+    if (rtx_film_save(film.f, blob.data(), blob.size(), &n) != RTX_OK)
+      throw std::runtime_error(std::string("rtx_film_save: ") + rtx_last_error());
+    std::ofstream o(checkpoint_, std::ios::binary);
+    o.write(blob.data(), (std::streamsize)n);
+    if (!o) throw std::runtime_error("cannot write " + checkpoint_);
+  }
   out.write(bytes.data(), (std::streamsize)len);
 }
 

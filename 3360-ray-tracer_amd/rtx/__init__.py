@@ -120,7 +120,10 @@ EXPORTS = ["rtx_abi_version", "rtx_last_error", "rtx_device_count", "rtx_scene_c
            "rtx_render_device", "rtx_host_scene_load", "rtx_host_scene_recipe", "rtx_host_scene_write",
            "rtx_host_scene_desc", "rtx_host_scene_prim_indices", "rtx_host_scene_destroy",
            "rtx_camera_config_load", "rtx_write_ppm", "rtx_p3_max_bytes", "rtx_render_p3", "rtx_encode_p3_device",
-           "rtx_prim_bounds", "rtx_bvh_build", "rtx_bvh_build_host", "rtx_render_multi", "rtx_encode_p3", "rtx_image_load"]
+           "rtx_prim_bounds", "rtx_bvh_build", "rtx_bvh_build_host", "rtx_render_multi", "rtx_encode_p3", "rtx_image_load",
+           "rtx_film_create", "rtx_film_destroy", "rtx_film_render", "rtx_film_samples", "rtx_film_resolve",
+           "rtx_film_resolve_device", "rtx_film_p3", "rtx_film_state_bytes", "rtx_film_save", "rtx_film_load",
+           "rtx_film_blob_check"]
 
 _lib = None
 
@@ -165,6 +168,17 @@ def lib():
                                   C.POINTER(Stats), vp], C.c_int),
             "rtx_encode_p3": ([vp, vp, i32, i32, vp, sz, C.POINTER(sz)], C.c_int),
             "rtx_image_load": ([C.c_char_p, i32, C.POINTER(i32), C.POINTER(i32), vp, sz], C.c_int),
+            "rtx_film_create": ([vp, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(vp)], C.c_int),
+            "rtx_film_destroy": ([vp], C.c_int),
+            "rtx_film_render": ([vp, i32, C.POINTER(Stats)], C.c_int),
+            "rtx_film_samples": ([vp, C.POINTER(i32)], C.c_int),
+            "rtx_film_resolve": ([vp, vp, vp], C.c_int),
+            "rtx_film_resolve_device": ([vp, vp, vp, vp], C.c_int),
+            "rtx_film_p3": ([vp, vp, sz, C.POINTER(sz)], C.c_int),
+            "rtx_film_state_bytes": ([vp], sz),
+            "rtx_film_save": ([vp, vp, sz, C.POINTER(sz)], C.c_int),
+            "rtx_film_load": ([vp, C.c_char_p, sz], C.c_int),
+            "rtx_film_blob_check": ([C.c_char_p, sz], C.c_int),
         }
         for name, (args, res) in sig.items():
             f = getattr(L, name)
@@ -285,6 +299,23 @@ class DeviceScene:
             _lib.rtx_scene_destroy(self.h)
             self.h = None
 
+    def film(self, cam, max_depth, seed=1234, adaptive=True, mode="wavefront", precision="parity", tile=None,
+             stripes=None, samples_per_group=0, min_spp=16, rel_threshold=float(np.float32(0.05)), schedule=None,
+             generic=False):
+        """A resumable frame on this scene (rtx_film_create): render(budget) advances it, and after
+        each call it equals the one-shot render(...) of the same arguments at spp = budget."""
+        p = RenderParams()
+        p.spp, p.max_depth, p.adaptive = 0, max_depth, int(bool(adaptive))
+        p.min_spp, p.rel_threshold, p.seed = min_spp, rel_threshold, seed
+        p.mode, p.precision = MODES[mode], PRECISIONS[precision]
+        p.samples_per_group = samples_per_group
+        p.flags = SCHEDULE_FLAGS[schedule] | (RTX_FLAG_GENERIC if generic else 0)
+        if stripes is not None:
+            p.stripe_rows, p.stripe_index, p.stripe_count = stripes
+        elif tile is not None:
+            p.x0, p.y0, p.w, p.h = tile
+        return Film(self, cam, p)
+
     def intersect(self, rays, tmin=RTX_SEAM_TMIN, tmax=float("inf"), precision="parity"):
         rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
         hits = np.zeros(len(rays), HIT_DTYPE)
@@ -350,6 +381,78 @@ class DeviceScene:
                                        C.c_void_p(d_spp) if d_spp else None, C.byref(st) if stats else None,
                                        C.c_void_p(stream) if stream else None), "rtx_render_device")
         return st.as_dict() if stats else None
+
+
+class Film:
+    """A frame rendered in steps (rtx_film_*): the per-pixel state stays on the scene's device
+    between calls.  Made by DeviceScene.film(); it keeps its scene alive."""
+
+    def __init__(self, scene, cam, params):
+        self.scene = scene
+        self.h = C.c_void_p()
+        n = lib().rtx_render_pixel_count(C.byref(cam), C.byref(params))
+        if n < 0:
+            _check(n, "rtx_render_pixel_count")
+        self.npix = n
+        self._p3_cap = lib().rtx_p3_max_bytes(cam.image_width, cam.image_height)
+        _check(lib().rtx_film_create(scene.h, C.byref(cam), C.byref(params), C.byref(self.h)), "rtx_film_create")
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.rtx_film_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def _handle(self):
+        if not self.h:
+            raise RtxError("the film is closed")
+        return self.h
+
+    def render(self, budget):
+        """Advance to `budget` samples per pixel; returns this call's statistics."""
+        st = Stats()
+        _check(lib().rtx_film_render(self._handle(), budget, C.byref(st)), "rtx_film_render")
+        return st.as_dict()
+
+    @property
+    def samples(self):
+        n = C.c_int32()
+        _check(lib().rtx_film_samples(self._handle(), C.byref(n)), "rtx_film_samples")
+        return n.value
+
+    def resolve(self):
+        """(rgb (npix, 3), spp (npix,)) at the current budget, in subset order."""
+        rgb = np.zeros((self.npix, 3))
+        spp = np.zeros(self.npix, np.int32)
+        _check(lib().rtx_film_resolve(self._handle(), rgb.ctypes.data_as(C.c_void_p), spp.ctypes.data_as(C.c_void_p)),
+               "rtx_film_resolve")
+        return rgb, spp
+
+    def p3(self):
+        """The P3 PPM file bytes of the current output, encoded on the device."""
+        buf = C.create_string_buffer(self._p3_cap)
+        n = C.c_size_t()
+        _check(lib().rtx_film_p3(self._handle(), buf, self._p3_cap, C.byref(n)), "rtx_film_p3")
+        return buf.raw[:n.value]
+
+    def save(self):
+        cap = lib().rtx_film_state_bytes(self._handle())
+        buf = C.create_string_buffer(cap)
+        n = C.c_size_t()
+        _check(lib().rtx_film_save(self.h, buf, cap, C.byref(n)), "rtx_film_save")
+        return buf.raw[:n.value]
+
+    def load(self, blob):
+        blob = bytes(blob)
+        _check(lib().rtx_film_load(self._handle(), blob, len(blob)), "rtx_film_load")
+
+
+def film_blob_check(blob):
+    """Header and length of a saved film (rtx_film_blob_check; no device needed): raises RtxError
+    naming what is wrong."""
+    blob = bytes(blob)
+    _check(lib().rtx_film_blob_check(blob, len(blob)), "rtx_film_blob_check")
 
 
 def adapt_tune(phase_slots=0, phase_kcap=0, first_map=-1, phase_mstep=-1.0, margin1=-1.0, pool_w=-1.0):

@@ -2,10 +2,16 @@
 //   raytracer [camera-preset] [--scene cornell|three|final|bunny|mixed|<file.rtxs>]
 //             [--cameras cameras.json] [--spp N] [--depth N] [--seed S] [--fixed]
 //             [--mode wavefront|persistent|megakernel] [--precision parity|fast]
-//             [--mk-adaptive MIN:THRESHOLD] [--gpus N] > out.ppm
+//             [--mk-adaptive MIN:THRESHOLD] [--gpus N]
+//             [--chunks N] [--preview PREFIX] [--checkpoint FILE] [--resume FILE] > out.ppm
 // --gpus N renders one frame over N GPUs (interleaved row stripes, one host thread per GPU,
 // one gathered framebuffer and P3 output; identical pixels for every N); --devices 0,2,3
 // names the devices (a device may repeat: several streams on one GPU).
+// --chunks N renders the frame in N steps (budgets ceil(k * spp / N)) through a film;
+// --preview PREFIX writes PREFIX_<budget>.ppm after each step; --checkpoint FILE saves the
+// film's state at the end and --resume FILE continues from a saved state (same scene, camera,
+// seed, depth and sampling).  The PPM on stdout is byte-identical to the plain run at the same
+// spp.  One GPU, wavefront / persistent modes.
 // --mk-adaptive selects the AdaptiveSampler (sampler.h:44-82) for --mode megakernel,
 // with max_samples = the preset's (or --spp) samples.
 // Defaults follow main.cc: preset "default" (fallback when unknown), the Cornell box
@@ -31,7 +37,8 @@ int main(int argc, char** argv) {
   uint64_t seed = 1234;
   bool fixed = false;
   std::vector<int> devices;
-  int mk_min = -1, gpus = 1;
+  int mk_min = -1, gpus = 1, chunks = 0;
+  std::string preview, checkpoint, resume;
   float mk_thr = 0.0f;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -51,6 +58,10 @@ int main(int argc, char** argv) {
     else if (a == "--precision") precision = next();
     else if (a == "--fixed") fixed = true;
     else if (a == "--gpus") gpus = std::atoi(next().c_str());
+    else if (a == "--chunks") chunks = std::atoi(next().c_str());
+    else if (a == "--preview") preview = next();
+    else if (a == "--checkpoint") checkpoint = next();
+    else if (a == "--resume") resume = next();
     else if (a == "--devices") {
       const std::string v = next();
       for (size_t p = 0; p < v.size();) {
@@ -96,6 +107,11 @@ int main(int argc, char** argv) {
       world = scene::BuildRecipe(scene_name, 1234, "");
     const int ns = spp > 0 ? spp : cam.samples_per_pixel_;
     const int md = depth >= 0 ? depth : cam.max_depth_;
+    const bool film = chunks > 0 || !preview.empty() || !checkpoint.empty() || !resume.empty();
+    if (film && mode == "megakernel") {
+      std::cerr << "--chunks / --preview / --checkpoint / --resume need --mode wavefront or persistent\n";
+      return 2;
+    }
     if (mode == "megakernel") {
       integrator::DefaultSampler fixed_sampler(ns);
       integrator::AdaptiveSampler adaptive_sampler(mk_min, ns, mk_thr);
@@ -114,6 +130,16 @@ int main(int argc, char** argv) {
       r.set_mode(mode == "persistent" ? RTX_MODE_PERSISTENT : RTX_MODE_WAVEFRONT);
       if (!devices.empty()) r.set_devices(devices);
       else if (gpus > 1) r.set_gpus(gpus);
+      if (film) r.set_progressive(chunks > 0 ? chunks : 1);
+      if (!checkpoint.empty()) r.set_checkpoint(checkpoint);
+      if (!resume.empty()) r.set_resume(resume);
+      if (!preview.empty())
+        r.set_preview([&](int budget, const std::string& p3) {
+          const std::string path = preview + "_" + std::to_string(budget) + ".ppm";
+          std::ofstream o(path, std::ios::binary);
+          o.write(p3.data(), (std::streamsize)p3.size());
+          if (!o) throw std::runtime_error("cannot write " + path);
+        });
       r.Render();
       std::clog << "Rays: " << r.stats().rays_total << " (" << r.stats().rays_total / (r.stats().kernel_ms * 1e3)
                 << " Mrays/s device)\n";

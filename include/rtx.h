@@ -14,6 +14,9 @@
  *       renderer/wavefront.h:22-45, renderer/wavefront.cc:40-242 (mode RTX_MODE_WAVEFRONT);
  *       MegaKernel(scene, camera, DefaultSampler).Render()
  *       renderer/mega_kernel.h:10-59 + integrator/sampler.h:22-34 (mode RTX_MODE_MEGAKERNEL).
+ *   rtx_film_* (no counterpart in the reference, whose Render() is one shot)
+ *       the same renders in steps: WavefrontRenderer's per-pixel PixelState
+ *       (renderer/pixel_state.h) kept between calls, resolved on demand, saved and loaded.
  *   rtx_scene_create
  *       the GPU hooks of the reference: Bvh::nodes()/prim_indices()/primitives() +
  *       BvhNodeGPU (geom/bvh.h:20-25,134-136), HittableType (geom/hittable.h:45-49).
@@ -365,6 +368,50 @@ int rtx_encode_p3_device(rtx_scene* scene, const double* d_rgb, int32_t width, i
    rtx_p3_max_bytes. */
 int rtx_encode_p3(rtx_scene* scene, const double* rgb, int32_t width, int32_t height, char* out, size_t cap,
                   size_t* out_len);
+
+/* ---- films: a frame rendered in steps (progressive preview, checkpoint / resume) ------------
+ * A film is the per-pixel render state (sum, mean, M2, samples, converged) of one frame, kept on
+ * the scene's device between calls.  rtx_render* starts that state, traces every sample and
+ * throws it away; a film keeps it, so a frame can be shown after a few samples and refined,
+ * stopped on a budget, extended later, or saved and continued in another process.  After
+ * rtx_film_render(film, b) the film is bit for bit what the one-shot render of the same
+ * parameters at spp = b holds, however the samples were split over calls (the RNG is keyed by
+ * (seed, pixel, sample) and every pixel records its samples in order).
+ * The scene lends its scratch (radiance slots, queues, the adaptive workspace); the film owns
+ * only the pixel state.  Films of one scene and the scene's own renders may alternate freely;
+ * like them, calls on one scene's films are serialised by the caller.  Destroying a scene
+ * frees its films' device memory: they stay valid handles for rtx_film_samples and
+ * rtx_film_destroy only, every other call returns RTX_ERR_INVALID. */
+typedef struct rtx_film rtx_film;
+/* A film over the pixel subset of params (rectangle or stripes) with its seed, max_depth, mode,
+ * precision, flags, samples_per_group, adaptive, min_spp and rel_threshold; params->spp is
+ * ignored.  RTX_MODE_MEGAKERNEL with adaptive is RTX_ERR_INVALID (AdaptiveSampler's spp + 1
+ * budget does not compose across calls). */
+int rtx_film_create(rtx_scene* scene, const rtx_camera* cam, const rtx_render_params* params, rtx_film** out);
+int rtx_film_destroy(rtx_film* film);
+/* Advance the film to `budget` samples: fixed sampling traces samples [done, budget) of every
+ * pixel; adaptive sampling continues every pixel that has not converged up to budget (the first
+ * call in phases, later ones in uniform groups).  budget <= done: nothing, RTX_OK.  stats (may be
+ * NULL: then the call does not wait for the device) covers this call only. */
+int rtx_film_render(rtx_film* film, int32_t budget, rtx_stats* stats);
+int rtx_film_samples(const rtx_film* film, int32_t* done);
+/* The film's output at its current budget, as rtx_render gives it (out_rgb 3 doubles per pixel
+ * in subset order, out_spp may be NULL).  Host buffers. */
+int rtx_film_resolve(rtx_film* film, double* out_rgb, int32_t* out_spp);
+/* Device buffers; stream is a hipStream_t (NULL = the scene's stream). */
+int rtx_film_resolve_device(rtx_film* film, double* d_out_rgb, int32_t* d_out_spp, void* stream);
+/* P3 file bytes of the film's output (device encoder, as rtx_render_p3); cap >= rtx_p3_max_bytes
+ * of the subset's width x rows. */
+int rtx_film_p3(rtx_film* film, char* out, size_t cap, size_t* out_len);
+/* Save / load: a host blob of rtx_film_state_bytes bytes, a little-endian header and the state
+ * arrays (layout: DESIGN.md "Film").  Load refuses (RTX_ERR_INVALID, the message names the
+ * field; the film is unchanged) a blob that is truncated or whose image size, pixel map, seed,
+ * max_depth, sampling parameters or sampler family differ from the film's. */
+size_t rtx_film_state_bytes(const rtx_film* film);
+int rtx_film_save(const rtx_film* film, void* blob, size_t cap, size_t* len);
+int rtx_film_load(rtx_film* film, const void* blob, size_t len);
+/* Header and length of a blob; host only, no device needed. */
+int rtx_film_blob_check(const void* blob, size_t len);
 
 /* write_color bytes (core/color.h:18-33) as a P3 PPM; rgb is a linear framebuffer (host). */
 int rtx_write_ppm(const char* path, const double* rgb, int32_t width, int32_t height);
