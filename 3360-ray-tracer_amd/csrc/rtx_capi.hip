@@ -17,6 +17,8 @@
 #include <vector>
 
 #include "rtx.h"
+#define RTX_DENOISE_AOV_KERNELS  // this translation unit holds k_aov (it needs the trace kernels)
+#include "rtx_denoise.h"
 #include "rtx_film.h"
 #include "rtx_frame_kernels.h"
 #include "rtx_p3.h"
@@ -200,11 +202,16 @@ struct rtx_film {
   int32_t done = 0;         // samples done: the film equals a one-shot render at spp = done
   DevBuf sum, mean, m2, samples, conv;  // mean / m2: adaptive films only
   mutable DevBuf stage;     // save / load: the blob's body on the device
+  // rtx_film_denoise*: the packed guide and albedo of the film's pixels (float4 each), made on
+  // first use; not part of the saved state
+  DevBuf dn_guide, dn_alb;
+  bool aov_ready = false;
   PixelSoA px() const {
     return PixelSoA{sum.as<double>(), mean.as<double>(), m2.as<double>(), samples.as<int32_t>(), conv.as<uint8_t>()};
   }
   void release() {
-    for (DevBuf* b : {&sum, &mean, &m2, &samples, &conv, &stage}) b->release();
+    for (DevBuf* b : {&sum, &mean, &m2, &samples, &conv, &stage, &dn_guide, &dn_alb}) b->release();
+    aov_ready = false;
   }
 };
 
@@ -228,6 +235,10 @@ struct rtx_scene {
   DevBuf px_sum, px_mean, px_m2, px_samples, px_conv, lbuf, queue[2], counters, out_rgb, out_spp, rays, hits;
   DevBuf p3_scratch, p3_body;  // device P3 encoding (rtx_p3.h)
   DevBuf patch_q;              // adaptive early output: the pixels still sampling when it went
+  // AOVs and the denoiser (rtx_denoise.h): the f64 AOVs of rtx_aov / a film's first denoise, the
+  // host entry points' staged inputs, an adaptive film's variance, and the filter's f32 working
+  // set: colour + variance ping-pong, guide, albedo
+  DevBuf aov_f64, dn_in, dn_var, dn_work[2], dn_guide, dn_alb;
   HostBuf stage_rgb, stage_spp;  // rtx_render_multi: pinned D2H staging of this device's stripes
   HostBuf counters_h;            // timed renders: pinned copy of the statistics counters (read after the end event)
   // ev[0] / ev[1]: a timed render's start and end (rtx_stats.kernel_ms), ev[2] / ev[3]: the
@@ -252,7 +263,8 @@ struct rtx_scene {
     (void)hipSetDevice(device);
     for (DevBuf* b : {&nodes, &prims, &mats, &texs, &images, &fnodes, &tri_n, &px_sum, &px_mean, &px_m2, &px_samples,
                       &px_conv, &lbuf, &queue[0], &queue[1], &counters, &out_rgb, &out_spp, &rays, &hits, &p3_scratch,
-                      &p3_body, &calib_rgb, &patch_q})
+                      &p3_body, &calib_rgb, &patch_q, &aov_f64, &dn_in, &dn_var, &dn_work[0], &dn_work[1], &dn_guide,
+                      &dn_alb})
       b->release();
     for (auto& t : texels) t.release();
     stage_rgb.release(), stage_spp.release();
@@ -654,6 +666,26 @@ int launch_intersect(rtx_scene* sc, const rtx_ray* d_rays, int64_t n, rtx_hit* d
   return RTX_OK;
 }
 
+template <int STACK, bool FAST>
+int launch_aov(rtx_scene* sc, const rtx_camera* cam, const PixelMap& map, int64_t npix, double* d_albedo,
+               double* d_normal, double* d_depth, hipStream_t s) {
+  hipLaunchKernelGGL((k_aov<STACK, FAST>), dim3((unsigned)((npix + kBlock - 1) / kBlock)), dim3(kBlock),
+                     stack_lds_bytes(STACK), s, sc->S, *cam, map, npix, (double)RTX_SEAM_TMIN, d_albedo, d_normal,
+                     d_depth);
+  HIPC(hipGetLastError());
+  return RTX_OK;
+}
+// k_aov over a pixel map, with the walk rtx_intersect_device picks for `precision`
+int aov_on(rtx_scene* sc, const rtx_camera* cam, const PixelMap& map, int64_t npix, int32_t precision, double* d_albedo,
+           double* d_normal, double* d_depth, hipStream_t s) {
+  if (npix == 0) return RTX_OK;
+  const bool fast = precision == RTX_PREC_FAST && sc->fast_ok;
+  const int st = fast ? sc->stack_fast : sc->stack_parity;
+  if (fast) return st == 32 ? launch_aov<32, true>(sc, cam, map, npix, d_albedo, d_normal, d_depth, s)
+                            : launch_aov<64, true>(sc, cam, map, npix, d_albedo, d_normal, d_depth, s);
+  return st == 32 ? launch_aov<32, false>(sc, cam, map, npix, d_albedo, d_normal, d_depth, s)
+                  : launch_aov<64, false>(sc, cam, map, npix, d_albedo, d_normal, d_depth, s);
+}
 int persistent_grid(rtx_scene* sc, const void* fn, size_t lds) {
   int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kBlock, lds) != hipSuccess || per_cu <= 0)
@@ -2133,6 +2165,192 @@ int rtx_film_load(rtx_film* f, const void* blob, size_t len) {
   if ((rc = film_pack(f, 0, s))) return rc;
   HIPC(hipStreamSynchronize(s));  // the blob is the caller's memory
   f->done = b.done;
+  return RTX_OK;
+}
+
+// ---- first-hit AOVs and the denoiser (rtx_denoise.h, DESIGN.md "AOVs and the denoiser") -------
+namespace {
+const rtx_denoise_params kDenoiseDefaults{5, RTX_DENOISE_DEMODULATE, 64.0, 0.05, 4.0};
+// Validated parameters as the kernels take them; *npix = w * h.
+int denoise_check(int32_t w, int32_t h, const rtx_denoise_params* p, rtxdn::FilterParams& f, int64_t* npix) {
+  if (w <= 0 || h <= 0) return fail(RTX_ERR_INVALID, "denoise: image size <= 0");
+  if ((int64_t)w * h >= 0x80000000ll) return fail(RTX_ERR_INVALID, "denoise: image of 2^31 pixels or more");
+  const rtx_denoise_params& q = p ? *p : kDenoiseDefaults;
+  if (q.iterations < 0 || q.iterations > rtxdn::kMaxIterations) return fail(RTX_ERR_INVALID, "denoise: iterations outside 0..8");
+  if (q.flags & ~RTX_DENOISE_DEMODULATE) return fail(RTX_ERR_INVALID, "denoise: unknown flags");
+  if (!(q.normal_power > 0) || !(q.sigma_depth > 0) || !(q.sigma_color > 0) || !std::isfinite(q.normal_power) ||
+      !std::isfinite(q.sigma_depth) || !std::isfinite(q.sigma_color))
+    return fail(RTX_ERR_INVALID, "denoise: normal_power and the sigmas must be positive");
+  f = rtxdn::FilterParams{q.iterations, q.flags, (float)q.normal_power, (float)q.sigma_depth, (float)q.sigma_color};
+  *npix = (int64_t)w * h;
+  return RTX_OK;
+}
+int denoise_work(rtx_scene* sc, int64_t npix, bool guides) {
+  int rc;
+  for (DevBuf& b : sc->dn_work)
+    if ((rc = b.reserve((size_t)npix * sizeof(float4)))) return rc;
+  if (guides)
+    for (DevBuf* b : {&sc->dn_guide, &sc->dn_alb})
+      if ((rc = b->reserve((size_t)npix * sizeof(float4)))) return rc;
+  return RTX_OK;
+}
+}  // namespace
+
+int rtx_denoise_params_default(rtx_denoise_params* out) {
+  if (!out) return fail(RTX_ERR_INVALID, "NULL argument");
+  *out = kDenoiseDefaults;
+  return RTX_OK;
+}
+
+int rtx_aov_device(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, double* d_albedo,
+                   double* d_normal, double* d_depth, void* stream) {
+  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
+  if (!cam || !prm) return fail(RTX_ERR_INVALID, "NULL argument");
+  PixelMap map;
+  std::string err;
+  const int64_t npix = subset_pixels(cam, prm, map, err);
+  if (npix < 0) return fail(RTX_ERR_INVALID, err);
+  HIPC(hipSetDevice(sc->device));
+  return aov_on(sc, cam, map, npix, prm->precision, d_albedo, d_normal, d_depth, stream ? (hipStream_t)stream : sc->stream);
+}
+
+int rtx_aov(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, double* albedo, double* normal,
+            double* depth) {
+  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
+  if (!cam || !prm) return fail(RTX_ERR_INVALID, "NULL argument");
+  PixelMap map;
+  std::string err;
+  const int64_t npix = subset_pixels(cam, prm, map, err);
+  if (npix < 0) return fail(RTX_ERR_INVALID, err);
+  if (npix == 0) return RTX_OK;
+  HIPC(hipSetDevice(sc->device));
+  int rc;
+  if ((rc = sc->aov_f64.reserve((size_t)npix * 7 * sizeof(double)))) return rc;
+  double* a = sc->aov_f64.as<double>();  // albedo 3 n, normal 3 n, depth n
+  double *n = a + 3 * npix, *d = a + 6 * npix;
+  hipStream_t s = sc->stream;
+  if ((rc = aov_on(sc, cam, map, npix, prm->precision, albedo ? a : nullptr, normal ? n : nullptr, depth ? d : nullptr, s)))
+    return rc;
+  if (albedo) HIPC(hipMemcpyAsync(albedo, a, (size_t)npix * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (normal) HIPC(hipMemcpyAsync(normal, n, (size_t)npix * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (depth) HIPC(hipMemcpyAsync(depth, d, (size_t)npix * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPC(hipStreamSynchronize(s));
+  return RTX_OK;
+}
+
+int rtx_denoise_device(rtx_scene* sc, int32_t w, int32_t h, const double* d_rgb, const double* d_albedo,
+                       const double* d_normal, const double* d_depth, const double* d_variance,
+                       const rtx_denoise_params* p, double* d_out, void* stream) {
+  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
+  if (!d_rgb || !d_albedo || !d_normal || !d_depth || !d_out) return fail(RTX_ERR_INVALID, "NULL buffer");
+  rtxdn::FilterParams f;
+  int64_t npix;
+  int rc;
+  if ((rc = denoise_check(w, h, p, f, &npix))) return rc;
+  HIPC(hipSetDevice(sc->device));
+  hipStream_t s = stream ? (hipStream_t)stream : sc->stream;
+  if (s != sc->stream) HIPC(hipStreamSynchronize(sc->stream));  // the working buffers may still be in use there
+  if (f.iterations > 0) {
+    if ((rc = denoise_work(sc, npix, true))) return rc;
+    HIPC(rtxdn::pack_guides(d_normal, d_depth, d_albedo, npix, sc->dn_guide.as<float4>(), sc->dn_alb.as<float4>(), s));
+  }
+  HIPC(rtxdn::filter(w, h, d_rgb, d_variance, sc->dn_guide.as<float4>(), sc->dn_alb.as<float4>(),
+                     sc->dn_work[0].as<float4>(), sc->dn_work[1].as<float4>(), f, d_out, s));
+  return RTX_OK;
+}
+
+int rtx_denoise(rtx_scene* sc, int32_t w, int32_t h, const double* rgb, const double* albedo, const double* normal,
+                const double* depth, const double* variance, const rtx_denoise_params* p, double* out) {
+  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
+  if (!rgb || !albedo || !normal || !depth || !out) return fail(RTX_ERR_INVALID, "NULL buffer");
+  rtxdn::FilterParams f;
+  int64_t npix;
+  int rc;
+  if ((rc = denoise_check(w, h, p, f, &npix))) return rc;
+  HIPC(hipSetDevice(sc->device));
+  if ((rc = sc->dn_in.reserve((size_t)npix * 11 * sizeof(double)))) return rc;
+  double* d = sc->dn_in.as<double>();  // rgb 3 n, albedo 3 n, normal 3 n, depth n, variance n
+  double *d_alb = d + 3 * npix, *d_nrm = d + 6 * npix, *d_dep = d + 9 * npix, *d_var = d + 10 * npix;
+  hipStream_t s = sc->stream;
+  const size_t one = (size_t)npix * sizeof(double);
+  HIPC(hipMemcpyAsync(d, rgb, 3 * one, hipMemcpyHostToDevice, s));
+  HIPC(hipMemcpyAsync(d_alb, albedo, 3 * one, hipMemcpyHostToDevice, s));
+  HIPC(hipMemcpyAsync(d_nrm, normal, 3 * one, hipMemcpyHostToDevice, s));
+  HIPC(hipMemcpyAsync(d_dep, depth, one, hipMemcpyHostToDevice, s));
+  if (variance) HIPC(hipMemcpyAsync(d_var, variance, one, hipMemcpyHostToDevice, s));
+  if ((rc = rtx_denoise_device(sc, w, h, d, d_alb, d_nrm, d_dep, variance ? d_var : nullptr, p, d, s))) return rc;
+  HIPC(hipMemcpyAsync(out, d, 3 * one, hipMemcpyDeviceToHost, s));
+  HIPC(hipStreamSynchronize(s));
+  return RTX_OK;
+}
+
+namespace {
+// The film's denoised frame into sc->out_rgb (device), enqueued on the scene's stream.
+int film_denoise_on(rtx_film* f, const rtx_denoise_params* p) {
+  int rc;
+  if ((rc = film_live(f))) return rc;
+  if (f->map.stripes) return fail(RTX_ERR_INVALID, "a stripe film cannot be denoised: stripes are not adjacent rows");
+  rtx_scene* sc = f->sc;
+  const int64_t npix = f->npix;
+  if ((rc = sc->out_rgb.reserve(std::max<int64_t>(1, npix) * 3 * sizeof(double)))) return rc;
+  if (npix == 0) return RTX_OK;
+  rtxdn::FilterParams fp;
+  int64_t n;
+  if ((rc = denoise_check(f->map.w, f->map.h, p, fp, &n))) return rc;
+  HIPC(hipSetDevice(f->device));
+  hipStream_t s = sc->stream;
+  if ((rc = film_resolve_on(f, sc->out_rgb.as<double>(), nullptr, s))) return rc;
+  if (fp.iterations == 0) return RTX_OK;  // the resolved frame itself
+  if ((rc = denoise_work(sc, npix, false))) return rc;
+  if (!f->aov_ready) {
+    for (DevBuf* b : {&f->dn_guide, &f->dn_alb})
+      if ((rc = b->reserve((size_t)npix * sizeof(float4)))) return rc;
+    if ((rc = sc->aov_f64.reserve((size_t)npix * 7 * sizeof(double)))) return rc;
+    double* a = sc->aov_f64.as<double>();
+    if ((rc = aov_on(sc, &f->cam, f->map, npix, f->prm.precision, a, a + 3 * npix, a + 6 * npix, s))) return rc;
+    HIPC(rtxdn::pack_guides(a + 3 * npix, a + 6 * npix, a, npix, f->dn_guide.as<float4>(), f->dn_alb.as<float4>(), s));
+    f->aov_ready = true;
+  }
+  const double* d_var = nullptr;
+  if (f->prm.adaptive) {  // a fixed-spp film keeps no M2
+    if ((rc = sc->dn_var.reserve((size_t)npix * sizeof(double)))) return rc;
+    hipLaunchKernelGGL(k_film_variance, dim3((unsigned)((npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, f->px(), npix,
+                       (const float4*)f->dn_alb.as<float4>(), fp.flags & RTX_DENOISE_DEMODULATE, sc->dn_var.as<double>());
+    HIPC(hipGetLastError());
+    d_var = sc->dn_var.as<double>();
+  }
+  HIPC(rtxdn::filter(f->map.w, f->map.h, sc->out_rgb.as<double>(), d_var, f->dn_guide.as<float4>(),
+                     f->dn_alb.as<float4>(), sc->dn_work[0].as<float4>(), sc->dn_work[1].as<float4>(), fp,
+                     sc->out_rgb.as<double>(), s));
+  return RTX_OK;
+}
+}  // namespace
+
+int rtx_film_denoise(rtx_film* f, const rtx_denoise_params* p, double* out_rgb) {
+  int rc;
+  if ((rc = film_live(f))) return rc;
+  if (!out_rgb) return fail(RTX_ERR_INVALID, "NULL argument");
+  if ((rc = film_denoise_on(f, p))) return rc;
+  rtx_scene* sc = f->sc;
+  HIPC(hipMemcpyAsync(out_rgb, sc->out_rgb.p, (size_t)f->npix * 3 * sizeof(double), hipMemcpyDeviceToHost, sc->stream));
+  HIPC(hipStreamSynchronize(sc->stream));
+  return RTX_OK;
+}
+
+int rtx_film_denoise_p3(rtx_film* f, const rtx_denoise_params* p, char* out, size_t cap, size_t* out_len) {
+  int rc;
+  if ((rc = film_live(f))) return rc;
+  if (!out || !out_len) return fail(RTX_ERR_INVALID, "NULL argument");
+  rtx_scene* sc = f->sc;
+  const std::string hd = p3_header(f->map.w, f->map.h);
+  if (cap < hd.size() + (size_t)f->npix * rtxp3::kMaxLine) return fail(RTX_ERR_INVALID, "output buffer below rtx_p3_max_bytes");
+  if ((rc = film_denoise_on(f, p))) return rc;
+  size_t body = 0;
+  if ((rc = p3_encode(sc, sc->out_rgb.as<double>(), f->npix, &body, sc->stream))) return rc;
+  std::memcpy(out, hd.data(), hd.size());
+  HIPC(hipMemcpyAsync(out + hd.size(), sc->p3_body.p, body, hipMemcpyDeviceToHost, sc->stream));
+  HIPC(hipStreamSynchronize(sc->stream));
+  *out_len = hd.size() + body;
   return RTX_OK;
 }
 

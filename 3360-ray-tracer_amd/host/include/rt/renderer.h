@@ -50,6 +50,10 @@ class WavefrontRenderer {
   void set_checkpoint(const std::string& path) { checkpoint_ = path; }
   void set_resume(const std::string& path) { resume_ = path; }
   void set_preview(std::function<void(int budget, const std::string& p3)> f) { preview_ = std::move(f); }
+  // The P3 output, and every preview, filtered by the edge-avoiding denoiser with its default
+  // parameters (rtx_film_denoise_p3: one device renders through a film; several devices: the
+  // gathered frame through rtx_aov + rtx_denoise).  framebuffer() stays the unfiltered frame.
+  void set_denoise(bool on) { denoise_ = on; }
   void set_seed(uint64_t s) { params_.seed = s; }
   void set_adaptive(bool on) { params_.adaptive = on ? 1 : 0; }
   void set_mode(int mode) { params_.mode = mode; }
@@ -71,6 +75,7 @@ class WavefrontRenderer {
   std::vector<rtx_scene*> extra_;     // their device-resident copies of the scene
   int stripe_rows_ = 8;
   int chunks_ = 0;                    // > 0: progressive (set_progressive)
+  bool denoise_ = false;              // set_denoise
   std::string checkpoint_, resume_;
   std::function<void(int, const std::string&)> preview_;
   void RenderFilm(integrator::GpuRayIntegrator* gpu, const rtx_render_params& p, std::ostream& out);

@@ -130,6 +130,10 @@ void WavefrontRenderer::Render(std::ostream& out) {
     RenderFilm(gpu, p, out);
     return;
   }
+  if (denoise_ && devices_.size() <= 1) {  // the film keeps the variance an adaptive frame is filtered with
+    RenderFilm(gpu, p, out);
+    return;
+  }
   std::string bytes(rtx_p3_max_bytes(dc.image_width, dc.image_height), '\0');
   size_t len = 0;
   if (devices_.size() > 1) {  // one frame over several devices, gathered on the host
@@ -145,11 +149,23 @@ void WavefrontRenderer::Render(std::ostream& out) {
     std::vector<rtx_scene*> all{gpu->device_scene()};
     all.insert(all.end(), extra_.begin(), extra_.end());
     p.stripe_rows = stripe_rows_, p.stripe_index = 0, p.stripe_count = 0;
-    if (rtx_render_multi(all.data(), (int32_t)all.size(), &dc, &p, rgb_.data(), spp_.data(), &stats_, nullptr) !=
-            RTX_OK ||
-        rtx_encode_p3(all[0], rgb_.data(), dc.image_width, dc.image_height, bytes.data(), bytes.size(), &len) !=
-            RTX_OK)
+    if (rtx_render_multi(all.data(), (int32_t)all.size(), &dc, &p, rgb_.data(), spp_.data(), &stats_, nullptr) != RTX_OK)
       throw std::runtime_error(std::string("rtx_render_multi: ") + rtx_last_error());
+    const double* frame = rgb_.data();
+    std::vector<double> clean;
+    if (denoise_) {  // the gathered frame, with the whole image's AOVs from the first device
+      rtx_render_params whole = p;
+      whole.stripe_rows = 0;
+      std::vector<double> alb(3 * n), nrm(3 * n), dep(n);
+      clean.resize(3 * n);
+      if (rtx_aov(all[0], &dc, &whole, alb.data(), nrm.data(), dep.data()) != RTX_OK ||
+          rtx_denoise(all[0], dc.image_width, dc.image_height, rgb_.data(), alb.data(), nrm.data(), dep.data(), nullptr,
+                      nullptr, clean.data()) != RTX_OK)
+        throw std::runtime_error(std::string("rtx_denoise: ") + rtx_last_error());
+      frame = clean.data();
+    }
+    if (rtx_encode_p3(all[0], frame, dc.image_width, dc.image_height, bytes.data(), bytes.size(), &len) != RTX_OK)
+      throw std::runtime_error(std::string("rtx_encode_p3: ") + rtx_last_error());
     out.write(bytes.data(), (std::streamsize)len);
     return;
   }
@@ -178,8 +194,9 @@ void WavefrontRenderer::RenderFilm(integrator::GpuRayIntegrator* gpu, const rtx_
   std::string bytes(rtx_p3_max_bytes(dc.image_width, dc.image_height), '\0');
   size_t len = 0;
   auto p3 = [&] {
-    if (rtx_film_p3(film.f, bytes.data(), bytes.size(), &len) != RTX_OK)
-      throw std::runtime_error(std::string("rtx_film_p3: ") + rtx_last_error());
+    const int rc = denoise_ ? rtx_film_denoise_p3(film.f, nullptr, bytes.data(), bytes.size(), &len)
+                            : rtx_film_p3(film.f, bytes.data(), bytes.size(), &len);
+    if (rc != RTX_OK) throw std::runtime_error(std::string(denoise_ ? "rtx_film_denoise_p3: " : "rtx_film_p3: ") + rtx_last_error());
   };
   const int chunks = chunks_ > 0 ? chunks_ : 1;
   stats_ = rtx_stats{};

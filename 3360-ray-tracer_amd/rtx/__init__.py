@@ -114,6 +114,14 @@ class Stats(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+RTX_DENOISE_DEMODULATE = 1
+
+
+class DenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("flags", C.c_int32), ("normal_power", C.c_double),
+                ("sigma_depth", C.c_double), ("sigma_color", C.c_double)]
+
+
 # Every entry point include/rtx.h declares (checked by tests/test_capi_exports.py).
 EXPORTS = ["rtx_abi_version", "rtx_last_error", "rtx_device_count", "rtx_scene_create", "rtx_scene_destroy",
            "rtx_intersect", "rtx_intersect_device", "rtx_camera_init", "rtx_render", "rtx_render_pixel_count",
@@ -123,7 +131,8 @@ EXPORTS = ["rtx_abi_version", "rtx_last_error", "rtx_device_count", "rtx_scene_c
            "rtx_prim_bounds", "rtx_bvh_build", "rtx_bvh_build_host", "rtx_render_multi", "rtx_encode_p3", "rtx_image_load",
            "rtx_film_create", "rtx_film_destroy", "rtx_film_render", "rtx_film_samples", "rtx_film_resolve",
            "rtx_film_resolve_device", "rtx_film_p3", "rtx_film_state_bytes", "rtx_film_save", "rtx_film_load",
-           "rtx_film_blob_check"]
+           "rtx_film_blob_check", "rtx_denoise_params_default", "rtx_aov", "rtx_aov_device", "rtx_denoise",
+           "rtx_denoise_device", "rtx_film_denoise", "rtx_film_denoise_p3"]
 
 _lib = None
 
@@ -179,6 +188,13 @@ def lib():
             "rtx_film_save": ([vp, vp, sz, C.POINTER(sz)], C.c_int),
             "rtx_film_load": ([vp, C.c_char_p, sz], C.c_int),
             "rtx_film_blob_check": ([C.c_char_p, sz], C.c_int),
+            "rtx_denoise_params_default": ([C.POINTER(DenoiseParams)], C.c_int),
+            "rtx_aov": ([vp, C.POINTER(Camera), C.POINTER(RenderParams), vp, vp, vp], C.c_int),
+            "rtx_aov_device": ([vp, C.POINTER(Camera), C.POINTER(RenderParams), vp, vp, vp, vp], C.c_int),
+            "rtx_denoise": ([vp, i32, i32, vp, vp, vp, vp, vp, C.POINTER(DenoiseParams), vp], C.c_int),
+            "rtx_denoise_device": ([vp, i32, i32, vp, vp, vp, vp, vp, C.POINTER(DenoiseParams), vp, vp], C.c_int),
+            "rtx_film_denoise": ([vp, C.POINTER(DenoiseParams), vp], C.c_int),
+            "rtx_film_denoise_p3": ([vp, C.POINTER(DenoiseParams), vp, sz, C.POINTER(sz)], C.c_int),
         }
         for name, (args, res) in sig.items():
             f = getattr(L, name)
@@ -324,6 +340,23 @@ class DeviceScene:
                "rtx_intersect")
         return hits
 
+    def aov(self, cam, tile=None, stripes=None, precision="parity"):
+        """First-hit AOVs of the pixel subset (rtx_aov), in subset order: (albedo (n, 3), normal
+        (n, 3), depth (n,)) from the ray through each pixel's centre."""
+        p = RenderParams()
+        p.precision = PRECISIONS[precision]
+        if stripes is not None:
+            p.stripe_rows, p.stripe_index, p.stripe_count = stripes
+        elif tile is not None:
+            p.x0, p.y0, p.w, p.h = tile
+        n = lib().rtx_render_pixel_count(C.byref(cam), C.byref(p))
+        if n < 0:
+            _check(n, "rtx_render_pixel_count")
+        albedo, normal, depth = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros(n)
+        _check(lib().rtx_aov(self.h, C.byref(cam), C.byref(p), albedo.ctypes.data_as(C.c_void_p),
+                             normal.ctypes.data_as(C.c_void_p), depth.ctypes.data_as(C.c_void_p)), "rtx_aov")
+        return albedo, normal, depth
+
     def render(self, cam, spp, max_depth, seed=1234, adaptive=True, mode="wavefront", precision="parity",
                tile=None, stripes=None, samples_per_group=0, min_spp=16, rel_threshold=float(np.float32(0.05)),
                count=False, schedule=None, generic=False, adapt_schedule=None):
@@ -436,6 +469,22 @@ class Film:
         _check(lib().rtx_film_p3(self._handle(), buf, self._p3_cap, C.byref(n)), "rtx_film_p3")
         return buf.raw[:n.value]
 
+    def denoise(self, **over):
+        """The current output filtered with the film's own first-hit AOVs (rtx_film_denoise):
+        (npix, 3) in subset order.  over: denoise_params fields.  The film is not changed."""
+        rgb = np.zeros((self.npix, 3))
+        _check(lib().rtx_film_denoise(self._handle(), C.byref(denoise_params(**over)), rgb.ctypes.data_as(C.c_void_p)),
+               "rtx_film_denoise")
+        return rgb
+
+    def denoise_p3(self, **over):
+        """The P3 PPM file bytes of denoise(**over), encoded on the device."""
+        buf = C.create_string_buffer(self._p3_cap)
+        n = C.c_size_t()
+        _check(lib().rtx_film_denoise_p3(self._handle(), C.byref(denoise_params(**over)), buf, self._p3_cap,
+                                         C.byref(n)), "rtx_film_denoise_p3")
+        return buf.raw[:n.value]
+
     def save(self):
         cap = lib().rtx_film_state_bytes(self._handle())
         buf = C.create_string_buffer(cap)
@@ -453,6 +502,36 @@ def film_blob_check(blob):
     naming what is wrong."""
     blob = bytes(blob)
     _check(lib().rtx_film_blob_check(blob, len(blob)), "rtx_film_blob_check")
+
+
+def denoise_params(**over):
+    """The denoiser's defaults (rtx_denoise_params_default) with fields replaced: iterations, flags,
+    normal_power, sigma_depth, sigma_color; demodulate=bool sets or clears RTX_DENOISE_DEMODULATE."""
+    p = DenoiseParams()
+    _check(lib().rtx_denoise_params_default(C.byref(p)), "rtx_denoise_params_default")
+    if "demodulate" in over:
+        on = over.pop("demodulate")
+        p.flags = (p.flags | RTX_DENOISE_DEMODULATE) if on else (p.flags & ~RTX_DENOISE_DEMODULATE)
+    for k, v in over.items():
+        if k not in dict(DenoiseParams._fields_):
+            raise TypeError(f"denoise_params: unknown field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def denoise(scene, rgb, albedo, normal, depth, width, height, variance=None, **over):
+    """Edge-avoiding a-trous filter of a width x height host image on `scene`'s device
+    (rtx_denoise): rgb, albedo, normal (n, 3), depth and the optional variance (n,), row-major;
+    over: denoise_params fields.  Returns the filtered (n, 3) image."""
+    n = width * height
+    arr = [np.ascontiguousarray(a, dtype=np.float64).reshape(n, k)
+           for a, k in ((rgb, 3), (albedo, 3), (normal, 3), (depth, 1))]
+    var = None if variance is None else np.ascontiguousarray(variance, dtype=np.float64).reshape(n)
+    out = np.zeros((n, 3))
+    _check(lib().rtx_denoise(scene.h, width, height, *[a.ctypes.data_as(C.c_void_p) for a in arr],
+                             None if var is None else var.ctypes.data_as(C.c_void_p),
+                             C.byref(denoise_params(**over)), out.ctypes.data_as(C.c_void_p)), "rtx_denoise")
+    return out
 
 
 def adapt_tune(phase_slots=0, phase_kcap=0, first_map=-1, phase_mstep=-1.0, margin1=-1.0, pool_w=-1.0):

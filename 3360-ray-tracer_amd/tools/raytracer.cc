@@ -3,7 +3,7 @@
 //             [--cameras cameras.json] [--spp N] [--depth N] [--seed S] [--fixed]
 //             [--mode wavefront|persistent|megakernel] [--precision parity|fast]
 //             [--mk-adaptive MIN:THRESHOLD] [--gpus N]
-//             [--chunks N] [--preview PREFIX] [--checkpoint FILE] [--resume FILE] > out.ppm
+//             [--chunks N] [--preview PREFIX] [--checkpoint FILE] [--resume FILE] [--denoise] > out.ppm
 // --gpus N renders one frame over N GPUs (interleaved row stripes, one host thread per GPU,
 // one gathered framebuffer and P3 output; identical pixels for every N); --devices 0,2,3
 // names the devices (a device may repeat: several streams on one GPU).
@@ -12,6 +12,9 @@
 // film's state at the end and --resume FILE continues from a saved state (same scene, camera,
 // seed, depth and sampling).  The PPM on stdout is byte-identical to the plain run at the same
 // spp.  One GPU, wavefront / persistent modes.
+// --denoise filters the PPM on stdout and every preview with the edge-avoiding denoiser at its
+// default parameters (first-hit albedo / normal / depth guides; an adaptive frame's own variance);
+// without it the bytes are those of the plain run.  Wavefront / persistent modes.
 // --mk-adaptive selects the AdaptiveSampler (sampler.h:44-82) for --mode megakernel,
 // with max_samples = the preset's (or --spp) samples.
 // Defaults follow main.cc: preset "default" (fallback when unknown), the Cornell box
@@ -35,7 +38,7 @@ int main(int argc, char** argv) {
               precision = "parity";
   int spp = -1, depth = -1;
   uint64_t seed = 1234;
-  bool fixed = false;
+  bool fixed = false, denoise = false;
   std::vector<int> devices;
   int mk_min = -1, gpus = 1, chunks = 0;
   std::string preview, checkpoint, resume;
@@ -62,6 +65,7 @@ int main(int argc, char** argv) {
     else if (a == "--preview") preview = next();
     else if (a == "--checkpoint") checkpoint = next();
     else if (a == "--resume") resume = next();
+    else if (a == "--denoise") denoise = true;
     else if (a == "--devices") {
       const std::string v = next();
       for (size_t p = 0; p < v.size();) {
@@ -112,6 +116,10 @@ int main(int argc, char** argv) {
       std::cerr << "--chunks / --preview / --checkpoint / --resume need --mode wavefront or persistent\n";
       return 2;
     }
+    if (denoise && mode == "megakernel") {
+      std::cerr << "--denoise needs --mode wavefront or persistent\n";
+      return 2;
+    }
     if (mode == "megakernel") {
       integrator::DefaultSampler fixed_sampler(ns);
       integrator::AdaptiveSampler adaptive_sampler(mk_min, ns, mk_thr);
@@ -133,6 +141,7 @@ int main(int argc, char** argv) {
       if (film) r.set_progressive(chunks > 0 ? chunks : 1);
       if (!checkpoint.empty()) r.set_checkpoint(checkpoint);
       if (!resume.empty()) r.set_resume(resume);
+      r.set_denoise(denoise);
       if (!preview.empty())
         r.set_preview([&](int budget, const std::string& p3) {
           const std::string path = preview + "_" + std::to_string(budget) + ".ppm";

@@ -413,6 +413,55 @@ int rtx_film_load(rtx_film* film, const void* blob, size_t len);
 /* Header and length of a blob; host only, no device needed. */
 int rtx_film_blob_check(const void* blob, size_t len);
 
+/* ---- first-hit AOVs and the denoiser (DESIGN.md "AOVs and the denoiser") ----------------------
+ * The geometry under each pixel, and an edge-avoiding a-trous wavelet filter guided by it, for
+ * frames shown at a few samples per pixel.  Nothing here changes a render's own result. */
+/* The AOVs of the pixel subset of params, in subset order like rtx_render, from the ray through
+ * each pixel's centre (origin cam->center, no lens sampling, no jitter): albedo (3 doubles per
+ * pixel: a Lambertian's texture value at the hit, a metal's albedo, 1 1 1 for dielectrics,
+ * lights and misses), normal (3: the hit record's, facing against the ray; 0 0 0 on a miss) and
+ * depth (1: t of the hit, 0 on a miss).  Only the pixel subset and `precision` of params are
+ * read.  Specular paths are not followed to a diffuse hit.  Any output may be NULL. */
+int rtx_aov(rtx_scene* scene, const rtx_camera* cam, const rtx_render_params* params, double* albedo,
+            double* normal, double* depth);
+/* Device buffers; stream is a hipStream_t (NULL = the scene's stream). */
+int rtx_aov_device(rtx_scene* scene, const rtx_camera* cam, const rtx_render_params* params, double* d_albedo,
+                   double* d_normal, double* d_depth, void* stream);
+
+enum { RTX_DENOISE_DEMODULATE = 1 }; /* filter colour / max(albedo, 1e-3), multiply back at the end */
+typedef struct {
+  int32_t iterations; /* 0..8; iteration k filters 5 x 5 taps at step 2^k; 0 copies the input */
+  int32_t flags;      /* RTX_DENOISE_* */
+  double normal_power; /* w_n = max(0, n_p . n_q)^normal_power */
+  double sigma_depth;  /* w_z = exp(-|z_p - z_q| / (sigma_depth max(z_p, z_q))) */
+  double sigma_color;  /* w_l = exp(-|lum_p - lum_q| / (sigma_color g_p + 1e-6)) */
+} rtx_denoise_params;
+/* iterations 5, normal_power 64, sigma_depth 0.05, sigma_color 4, RTX_DENOISE_DEMODULATE.  Host only. */
+int rtx_denoise_params_default(rtx_denoise_params* out);
+/* Filter a width x height image on the scene's device: rgb, albedo and normal 3 doubles per
+ * pixel, depth 1, row-major; variance (1 per pixel, may be NULL) is the variance of each pixel's
+ * estimate in the filtered domain (of colour / albedo with RTX_DENOISE_DEMODULATE) and scales the
+ * colour distance, g_p = sqrt of its 3 x 3 Gaussian; without it g_p = 1.  params NULL: the
+ * defaults.  The working buffers are f32 and belong to the scene.  iterations outside 0..8, a
+ * sigma or power that is not positive, and width * height >= 2^31 are RTX_ERR_INVALID.  out
+ * (3 doubles per pixel) may be rgb.  Host buffers. */
+int rtx_denoise(rtx_scene* scene, int32_t width, int32_t height, const double* rgb, const double* albedo,
+                const double* normal, const double* depth, const double* variance, const rtx_denoise_params* params,
+                double* out);
+/* Device buffers; asynchronous on stream (NULL = the scene's stream). */
+int rtx_denoise_device(rtx_scene* scene, int32_t width, int32_t height, const double* d_rgb, const double* d_albedo,
+                       const double* d_normal, const double* d_depth, const double* d_variance,
+                       const rtx_denoise_params* params, double* d_out, void* stream);
+/* The film's output (rtx_film_resolve) filtered with the AOVs of its own camera and pixel
+ * rectangle, computed on first use and kept with the film (not part of its saved state).  An
+ * adaptive film passes the variance of its estimate: var_c = m2_c / (n - 1) / n for n >= 2 else
+ * 0, var = sum_c lumweight_c^2 var_c, divided by lum(max(albedo, 1e-3))^2 when demodulating.
+ * The film's state is not changed.  A stripe film is RTX_ERR_INVALID (stripes are not adjacent
+ * rows).  out_rgb: host, subset order. */
+int rtx_film_denoise(rtx_film* film, const rtx_denoise_params* params, double* out_rgb);
+/* The same frame as P3 file bytes (as rtx_film_p3). */
+int rtx_film_denoise_p3(rtx_film* film, const rtx_denoise_params* params, char* out, size_t cap, size_t* out_len);
+
 /* write_color bytes (core/color.h:18-33) as a P3 PPM; rgb is a linear framebuffer (host). */
 int rtx_write_ppm(const char* path, const double* rgb, int32_t width, int32_t height);
 
