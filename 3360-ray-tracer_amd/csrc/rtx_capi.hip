@@ -613,6 +613,61 @@ int pick_stack(int depth) {
   return -1;
 }
 
+// The reference-layout nodes' indices, checked so that neither the host routines below nor the
+// kernels read out of bounds: nullptr, or what is wrong.
+const char* bad_nodes(const rtx_scene_desc* d) {
+  for (int64_t i = 0; i < d->n_nodes; i++) {
+    const rtx_bvh_node& n = d->nodes[i];
+    if (n.is_leaf) {
+      if ((int64_t)n.left_first + n.right_count > d->n_prims) return "leaf range out of bounds";
+    } else if (n.left_first >= d->n_nodes || n.right_count >= d->n_nodes || n.left_first <= i || n.right_count <= i) {
+      return "child index out of bounds (nodes must be pre-order)";
+    }
+  }
+  return nullptr;
+}
+
+// What rtx_scene_create decides on the host about a scene's traversal, and the fast tree it
+// uploads: one routine, shared with the test hook rtx_internal_fast_tree, so the hook reports
+// the product's own tree.  No HIP call.
+struct FastPlan {
+  int depth = 0;                    // levels of the reference-layout tree (bvh_depth)
+  int stack_parity = 32;            // pick_stack(depth), -1: deeper than the parity walk's largest stack
+  int stack_fast = 32, fast_need = 0;
+  bool fast_ok = false;             // RTX_PREC_FAST has a tree and a stack for it
+  std::vector<F4Node> f4;           // built whenever the root is internal, also when fast_ok is false
+  int32_t global[2] = {0, 0};
+  int n_global = 0;                 // globals the tree was built without (the scene uses them only with fast_ok)
+  int tree_kind = -1;               // the one kind of the tree's primitives with fast_ok, else -1
+};
+void plan_fast_tree(const rtx_scene_desc* d, FastPlan& p) {
+  p = FastPlan{};
+  if (!(d->nodes && d->n_nodes > 0)) return;
+  p.depth = bvh_depth(d->nodes, d->n_nodes);
+  p.stack_parity = pick_stack(p.depth);
+  p.stack_fast = p.stack_parity;
+  if (p.stack_parity < 0) return;
+  if (!d->nodes[0].is_leaf) {
+    // the fast path's tree: our own binned SAH tree over the primitives (without the global
+    // ones), collapsed to BVH4 (r01: +2 % C2 / bunny, +6 % C5 over collapsing the reference's)
+    std::vector<rtx_bvh_node> own;
+    p.n_global = build_global_prims(d->prims, d->n_prims, p.global);
+    build_own_sah(d->prims, d->n_prims, p.global, p.n_global, own);
+    const int need = build_fast4(own.data(), d->prims, p.f4);
+    p.stack_fast = need < 0 ? -1 : (need <= 32 ? 32 : (need <= 64 ? 64 : -1));
+    p.fast_need = need;
+    p.fast_ok = p.stack_fast > 0;
+  }
+  if (p.fast_ok && d->n_prims > 0) {  // the one kind of the tree's primitives (globals excluded)
+    int k = -2;
+    for (int64_t i = 0; i < d->n_prims && k != -1; i++) {
+      if ((p.n_global > 0 && p.global[0] == i) || (p.n_global > 1 && p.global[1] == i)) continue;
+      k = k == -2 ? d->prims[i].kind : (k == d->prims[i].kind ? k : -1);
+    }
+    p.tree_kind = k < 0 ? -1 : k;
+  }
+}
+
 template <class T>
 int upload(DevBuf& b, const T* src, size_t n, hipStream_t s) {
   int rc = b.reserve(std::max<size_t>(n * sizeof(T), 16));
@@ -1042,14 +1097,7 @@ int rtx_scene_create(int device, const rtx_scene_desc* d, rtx_scene** out) {
     if (im.width < 0 || im.height < 0) return fail(RTX_ERR_INVALID, "negative image size");
     if ((int64_t)im.width * im.height > (1ll << 31)) return fail(RTX_ERR_INVALID, "image above 2^31 texels");
   }
-  for (int64_t i = 0; i < d->n_nodes; i++) {
-    const rtx_bvh_node& n = d->nodes[i];
-    if (n.is_leaf) {
-      if ((int64_t)n.left_first + n.right_count > d->n_prims) return fail(RTX_ERR_INVALID, "leaf range out of bounds");
-    } else if (n.left_first >= d->n_nodes || n.right_count >= d->n_nodes || n.left_first <= i || n.right_count <= i) {
-      return fail(RTX_ERR_INVALID, "child index out of bounds (nodes must be pre-order)");
-    }
-  }
+  if (const char* why = bad_nodes(d)) return fail(RTX_ERR_INVALID, why);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(RTX_ERR_NODEVICE, "no HIP device");
   if (device < 0 || device >= ndev) return fail(RTX_ERR_INVALID, "device out of range");
@@ -1132,29 +1180,23 @@ int rtx_scene_create(int device, const rtx_scene_desc* d, rtx_scene** out) {
   }
   if ((rc = upload(sc->images, imgs.data(), imgs.size(), s))) return rc;
   sc->n_nodes = d->nodes ? d->n_nodes : 0;
-  std::vector<F4Node> f4;
-  int32_t global[2] = {0, 0};
-  int n_global = 0;
+  FastPlan plan;
+  const std::vector<F4Node>& f4 = plan.f4;
+  const int32_t* global = plan.global;
   if (d->nodes && d->n_nodes > 0) {
     if ((rc = upload(sc->nodes, d->nodes, d->n_nodes, s))) return rc;
-    const int depth = bvh_depth(d->nodes, d->n_nodes);
-    sc->stack_parity = pick_stack(depth);
-    sc->stack_fast = sc->stack_parity;
+    plan_fast_tree(d, plan);
+    sc->stack_parity = plan.stack_parity;
+    sc->stack_fast = plan.stack_fast;
     if (sc->stack_parity < 0) return fail(RTX_ERR_INVALID, "BVH deeper than 62 levels");
     if (!d->nodes[0].is_leaf) {
-      // the fast path's tree: our own binned SAH tree over the primitives (without the global
-      // ones), collapsed to BVH4 (r01: +2 % C2 / bunny, +6 % C5 over collapsing the reference's)
-      std::vector<rtx_bvh_node> own;
-      n_global = build_global_prims(d->prims, d->n_prims, global);
-      build_own_sah(d->prims, d->n_prims, global, n_global, own);
-      const int need = build_fast4(own.data(), d->prims, f4);
-      sc->stack_fast = need < 0 ? -1 : (need <= 32 ? 32 : (need <= 64 ? 64 : -1));
-      sc->fast_need = need;
+      sc->fast_need = plan.fast_need;
       sc->n_f4 = f4.size();
-      if (sc->stack_fast > 0 && (rc = upload(sc->fnodes, f4.data(), f4.size(), s))) return rc;
-      sc->fast_ok = sc->stack_fast > 0;
+      if (plan.fast_ok && (rc = upload(sc->fnodes, f4.data(), f4.size(), s))) return rc;
+      sc->fast_ok = plan.fast_ok;
     }
   }
+  const int n_global = plan.n_global;
   HIPC(hipStreamSynchronize(s));
   DScene& S = sc->S;
   S.nodes = sc->nodes.as<rtx_bvh_node>();
@@ -1175,15 +1217,7 @@ int rtx_scene_create(int device, const rtx_scene_desc* d, rtx_scene** out) {
   S.no_textures = 1;
   for (const rtx_material& m : dmats)
     if ((m.kind == RTX_MAT_LAMBERTIAN || m.kind == RTX_MAT_DIFFUSE_LIGHT) && m.texture >= 0) S.no_textures = 0;
-  S.tree_kind = -1;
-  if (sc->fast_ok && d->n_prims > 0) {  // the one kind of the tree's primitives (globals excluded)
-    int k = -2;
-    for (int64_t i = 0; i < d->n_prims && k != -1; i++) {
-      if ((n_global > 0 && global[0] == i) || (n_global > 1 && global[1] == i)) continue;
-      k = k == -2 ? d->prims[i].kind : (k == d->prims[i].kind ? k : -1);
-    }
-    S.tree_kind = k < 0 ? -1 : k;
-  }
+  S.tree_kind = plan.tree_kind;  // the one kind of the tree's primitives (globals excluded)
   S.global[0] = global[0], S.global[1] = global[1];
   for (int64_t i = 0; i < d->n_prims && !S.has_tris; i++) S.has_tris = d->prims[i].kind == RTX_PRIM_TRIANGLE;
   if (S.use_bvh && d->nodes[0].is_leaf) S.froot_leaf = 1, S.froot_count = (int32_t)d->nodes[0].right_count;
@@ -2506,6 +2540,34 @@ extern "C" int rtx_internal_lds_layout(int stack_slots, int park, uint32_t* out)
   const uint32_t v[11] = {l.stack, l.thr, l.hitp, l.leafq, l.block, l.end, (uint32_t)stack_slots * (spec ? 2u : 4u),
                           24u, 24u, spec ? kLeafQueue * 4u : 0u, block_region_bytes(block_kind)};
   std::memcpy(out, v, sizeof v);
+  return RTX_OK;
+}
+
+// Test hook (not in rtx.h): the host-side traversal plan rtx_scene_create makes for `desc`
+// (plan_fast_tree, the routine rtx_scene_create itself runs), without a device.
+// info[0..9] = stack_parity (-1: the tree is deeper than 62 levels and rtx_scene_create refuses
+// it), depth, fast_ok, stack_fast, fast_need, n_f4, n_global, global[0], global[1], tree_kind.
+// n_global counts the primitives the fast tree was built without, also when fast_ok is 0 (the
+// scene then serves fast requests with the parity walk and uses neither tree nor globals).
+// f4_out (may be null: a size query) receives the first min(n_f4, f4_cap) F4Nodes, 128 bytes
+// each (rtx_device.h); they are built whenever the reference-layout root is internal and the
+// depth is accepted, so a tree that needs more than 64 stack entries can still be inspected.
+extern "C" int rtx_internal_fast_tree(const rtx_scene_desc* desc, int32_t* info, void* f4_out, int64_t f4_cap) {
+  if (!desc || !info) return fail(RTX_ERR_INVALID, "NULL argument");
+  if (desc->n_prims < 0 || desc->n_nodes < 0 || (desc->n_prims > 0 && !desc->prims))
+    return fail(RTX_ERR_INVALID, "bad scene description");
+  if (desc->n_nodes > 0 && !desc->nodes) return fail(RTX_ERR_INVALID, "nodes is NULL");
+  for (int64_t i = 0; i < desc->n_prims; i++)
+    if (desc->prims[i].kind < RTX_PRIM_SPHERE || desc->prims[i].kind > RTX_PRIM_YZ_RECT)
+      return fail(RTX_ERR_INVALID, "bad primitive kind");
+  if (const char* why = bad_nodes(desc)) return fail(RTX_ERR_INVALID, why);
+  FastPlan p;
+  plan_fast_tree(desc, p);
+  const int32_t v[10] = {p.stack_parity, p.depth, p.fast_ok ? 1 : 0, p.stack_fast, p.fast_need, (int32_t)p.f4.size(),
+                         p.n_global, p.global[0], p.global[1], p.tree_kind};
+  std::memcpy(info, v, sizeof v);
+  if (f4_out && f4_cap > 0)
+    std::memcpy(f4_out, p.f4.data(), (size_t)std::min<int64_t>(f4_cap, (int64_t)p.f4.size()) * sizeof(F4Node));
   return RTX_OK;
 }
 

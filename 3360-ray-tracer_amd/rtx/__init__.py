@@ -643,6 +643,34 @@ def stripe_rows_of(height, stripe_rows, index, count, width=1):
     return [int(y) for y in rows[:n.value]]
 
 
+F4NODE_DTYPE = np.dtype([("lox", "<f4", 4), ("hix", "<f4", 4), ("loy", "<f4", 4), ("hiy", "<f4", 4),
+                         ("loz", "<f4", 4), ("hiz", "<f4", 4), ("child", "<i4", 4), ("counts", "<u4", 2),
+                         ("pad_", "<u4", 2)])
+assert F4NODE_DTYPE.itemsize == 128
+FAST_TREE_INFO = ("stack_parity", "depth", "fast_ok", "stack_fast", "fast_need", "n_f4", "n_global", "global0",
+                  "global1", "tree_kind")
+
+
+def fast_tree(scene):
+    """Test hook (rtx_internal_fast_tree, not in rtx.h): the host-side traversal plan that
+    rtx_scene_create makes for a scene, without a device.  scene: a SceneDesc, or anything with
+    a .desc() method (a HostScene).  Returns (info dict, F4Node array): stack_parity (-1: deeper
+    than 62 levels, rtx_scene_create refuses the scene), depth, fast_ok, stack_fast, fast_need,
+    n_f4, n_global, global0, global1, tree_kind, and the fast tree's nodes (F4NODE_DTYPE; layout
+    in csrc/rtx_device.h), which exist whenever the reference-layout root is internal."""
+    d = scene if isinstance(scene, SceneDesc) else scene.desc()
+    f = lib().rtx_internal_fast_tree
+    f.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_int64]
+    f.restype = C.c_int
+    info = np.zeros(len(FAST_TREE_INFO), np.int32)
+    _check(f(C.byref(d), info.ctypes.data_as(C.c_void_p), None, 0), "rtx_internal_fast_tree")
+    nodes = np.zeros(int(info[5]), F4NODE_DTYPE)
+    if len(nodes):
+        _check(f(C.byref(d), info.ctypes.data_as(C.c_void_p), nodes.ctypes.data_as(C.c_void_p), len(nodes)),
+               "rtx_internal_fast_tree")
+    return {k: int(v) for k, v in zip(FAST_TREE_INFO, info)}, nodes
+
+
 def write_ppm(path, rgb, width, height):
     rgb = np.ascontiguousarray(rgb, dtype=np.float64)
     _check(lib().rtx_write_ppm(path.encode(), rgb.ctypes.data_as(C.c_void_p), width, height), "rtx_write_ppm")
