@@ -17,6 +17,8 @@
 #include <vector>
 
 #include "rtx.h"
+#include "rtx_bounds.h"
+#include "rtx_refit.h"
 #define RTX_DENOISE_AOV_KERNELS  // this translation unit holds k_aov (it needs the trace kernels)
 #include "rtx_denoise.h"
 #include "rtx_film.h"
@@ -103,16 +105,8 @@ struct HostBuf {  // pinned host staging (grow-only)
   }
 };
 
-float round_down(double x) {
-  float f = (float)x;
-  if ((double)f > x) f = std::nextafter(f, -INFINITY);
-  return f;
-}
-float round_up(double x) {
-  float f = (float)x;
-  if ((double)f < x) f = std::nextafter(f, INFINITY);
-  return f;
-}
+using rtxb::round_down;
+using rtxb::round_up;
 
 }  // namespace
 
@@ -200,6 +194,7 @@ struct rtx_film {
   PixelMap map{};
   int64_t npix = 0;
   int32_t done = 0;         // samples done: the film equals a one-shot render at spp = done
+  int64_t epoch = 0;        // the scene's epoch the film was created or last reset at (rtx_film_reset)
   DevBuf sum, mean, m2, samples, conv;  // mean / m2: adaptive films only
   mutable DevBuf stage;     // save / load: the blob's body on the device
   // rtx_film_denoise*: the packed guide and albedo of the film's pixels (float4 each), made on
@@ -221,6 +216,16 @@ struct rtx_scene {
   hipStream_t stream = nullptr;
   int cus = 0;
   DevBuf nodes, prims, mats, texs, images, fnodes, tri_n;
+  // kept for rtx_scene_update_* (DESIGN.md §4c), scenes with nodes: each primitive's reference
+  // box (6 doubles, rtx_prim_bounds) and conservative fast box (6 floats, prim_box rounded
+  // outward), and both trees' node indices grouped by height (a node without child nodes has
+  // height 0); *_lvl: where each height starts in its index array, and the end
+  DevBuf ref_box, fast_box, node_order, f4_order, upd_stage;
+  std::vector<int64_t> node_lvl, f4_lvl;
+  HostBuf upd_host;            // rtx_scene_update_prims: pinned staging of the caller's records
+  std::vector<int8_t> kinds;   // each primitive's kind (an update may not change it)
+  int32_t n_materials = 0;
+  int64_t epoch = 0;           // updates applied so far
   DevBuf segs1;  // counting adaptive renders: the first phase's per-slot path segments (u16)
   std::vector<DevBuf> texels;
   DScene S{};
@@ -261,6 +266,8 @@ struct rtx_scene {
     for (auto e : band_ev) (void)hipEventDestroy(e);
     if (copy_stream) (void)hipStreamDestroy(copy_stream);
     (void)hipSetDevice(device);
+    for (DevBuf* b : {&ref_box, &fast_box, &node_order, &f4_order, &upd_stage}) b->release();
+    upd_host.release();
     for (DevBuf* b : {&nodes, &prims, &mats, &texs, &images, &fnodes, &tri_n, &px_sum, &px_mean, &px_m2, &px_samples,
                       &px_conv, &lbuf, &queue[0], &queue[1], &counters, &out_rgb, &out_spp, &rays, &hits, &p3_scratch,
                       &p3_body, &calib_rgb, &patch_q, &aov_f64, &dn_in, &dn_var, &dn_work[0], &dn_work[1], &dn_guide,
@@ -291,36 +298,9 @@ int bvh_depth(const rtx_bvh_node* n, int64_t count) {
   return m;
 }
 
-// Conservative f64 box of one primitive (fast-path leaf splitting).  Spheres: centre +-
-// |r|; rects: the rectangle on its plane; triangles: the vertex box padded by 2^-19 of its
-// largest extent, which covers the points the reference's float-rounded barycentric test
-// accepts just outside the exact triangle (u, v, u + v within 2^-23 of the edges).
-void prim_box(const rtx_prim& p, double lo[3], double hi[3]) {
-  const double* g = p.g;
-  if (p.kind == RTX_PRIM_SPHERE) {
-    const double r = std::fabs(g[3]);
-    for (int a = 0; a < 3; a++) lo[a] = g[a] - r, hi[a] = g[a] + r;
-    return;
-  }
-  if (p.kind == RTX_PRIM_TRIANGLE) {
-    double ext = 0;
-    for (int a = 0; a < 3; a++) {
-      lo[a] = std::min(g[a], std::min(g[3 + a], g[6 + a]));
-      hi[a] = std::max(g[a], std::max(g[3 + a], g[6 + a]));
-      ext = std::max(ext, hi[a] - lo[a]);
-    }
-    const double pad = std::ldexp(ext, -19);
-    for (int a = 0; a < 3; a++) lo[a] -= pad, hi[a] += pad;
-    return;
-  }
-  int ax, a0, a1;  // rect.h: XY (z = k), XZ (y = k), YZ (x = k)
-  if (p.kind == RTX_PRIM_XY_RECT) ax = 2, a0 = 0, a1 = 1;
-  else if (p.kind == RTX_PRIM_XZ_RECT) ax = 1, a0 = 0, a1 = 2;
-  else ax = 0, a0 = 1, a1 = 2;
-  lo[a0] = std::min(g[0], g[1]), hi[a0] = std::max(g[0], g[1]);
-  lo[a1] = std::min(g[2], g[3]), hi[a1] = std::max(g[2], g[3]);
-  lo[ax] = hi[ax] = g[4];
-}
+// Conservative f64 box of one primitive (fast-path leaf splitting): rtx_bounds.h, shared with
+// the refit kernels.
+void prim_box(const rtx_prim& p, double lo[3], double hi[3]) { rtxb::prim_box(p.kind, p.g, lo, hi); }
 
 // BVH4 fast layout: the binary tree collapsed top-down.  Each F4Node starts from the binary
 // node's two children and repeatedly opens the slot with the largest surface area until it
@@ -674,6 +654,19 @@ int upload(DevBuf& b, const T* src, size_t n, hipStream_t s) {
   if (rc) return rc;
   if (n) HIPC(hipMemcpyAsync(b.p, src, n * sizeof(T), hipMemcpyHostToDevice, s));
   return RTX_OK;
+}
+
+// Node indices sorted by height (stable), and where each height starts: lvl[k] .. lvl[k + 1] are
+// the nodes of height k in `order`.
+void group_by_height(const std::vector<int>& h, std::vector<uint32_t>& order, std::vector<int64_t>& lvl) {
+  int top = 0;
+  for (int v : h) top = std::max(top, v);
+  lvl.assign((size_t)top + 2, 0);
+  for (int v : h) lvl[(size_t)v + 1]++;
+  for (size_t k = 1; k < lvl.size(); k++) lvl[k] += lvl[k - 1];
+  order.resize(h.size());
+  std::vector<int64_t> at(lvl.begin(), lvl.end() - 1);
+  for (size_t i = 0; i < h.size(); i++) order[(size_t)at[h[i]]++] = (uint32_t)i;
 }
 
 int64_t subset_pixels(const rtx_camera* cam, const rtx_render_params* p, PixelMap& m, std::string& err) {
@@ -1122,14 +1115,9 @@ int rtx_scene_create(int device, const rtx_scene_desc* d, rtx_scene** out) {
     for (int64_t i = 0; i < d->n_prims; i++) {
       const rtx_prim& q = d->prims[i];
       if (q.kind != RTX_PRIM_TRIANGLE) continue;
-      double e1[3], e2[3];
-      for (int a = 0; a < 3; a++) e1[a] = q.g[3 + a] - q.g[a], e2[a] = q.g[6 + a] - q.g[a];
-      const double c[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2],
-                           e1[0] * e2[1] - e1[1] * e2[0]};
-      const double l = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
-      if (l == 0.0) continue;  // normalize() returns (0, 0, 0)
-      const double inv = 1.0 / l;
-      for (int a = 0; a < 3; a++) tn[4 * (size_t)i + a] = inv * c[a];
+      double nrm[3];
+      rtxb::tri_unit_normal(q.g, nrm);  // (0, 0, 0) for a zero length, as normalize() returns
+      for (int a = 0; a < 3; a++) tn[4 * (size_t)i + a] = nrm[a];
     }
     if ((rc = upload(sc->tri_n, tn.data(), tn.size(), s))) return rc;
     HIPC(hipStreamSynchronize(s));  // tn is a temporary
@@ -1196,6 +1184,36 @@ int rtx_scene_create(int device, const rtx_scene_desc* d, rtx_scene** out) {
       sc->fast_ok = plan.fast_ok;
     }
   }
+  // what an in-place update needs (rtx_scene_update_*): the primitives' boxes as the builders saw
+  // them, and both trees' nodes by height
+  sc->kinds.resize((size_t)d->n_prims);
+  for (int64_t i = 0; i < d->n_prims; i++) sc->kinds[i] = (int8_t)d->prims[i].kind;
+  sc->n_materials = d->n_materials;
+  std::vector<double> rbox;
+  std::vector<float> fbox;
+  std::vector<uint32_t> norder, forder;
+  if (sc->n_nodes > 0) {
+    rbox.resize((size_t)d->n_prims * 6), fbox.resize((size_t)d->n_prims * 6);
+    for (int64_t i = 0; i < d->n_prims; i++) {
+      rtxb::ref_bounds(d->prims[i].kind, d->prims[i].g, &rbox[6 * (size_t)i]);
+      rtxb::fast_box(d->prims[i].kind, d->prims[i].g, &fbox[6 * (size_t)i]);
+    }
+    if ((rc = upload(sc->ref_box, rbox.data(), rbox.size(), s))) return rc;
+    if ((rc = upload(sc->fast_box, fbox.data(), fbox.size(), s))) return rc;
+    std::vector<int> h((size_t)d->n_nodes, 0);
+    for (int64_t i = d->n_nodes - 1; i >= 0; i--)  // pre-order (bad_nodes): children come later
+      if (!d->nodes[i].is_leaf) h[i] = 1 + std::max(h[d->nodes[i].left_first], h[d->nodes[i].right_count]);
+    group_by_height(h, norder, sc->node_lvl);
+    if ((rc = upload(sc->node_order, norder.data(), norder.size(), s))) return rc;
+    if (sc->fast_ok) {
+      h.assign(f4.size(), 0);
+      for (int64_t i = (int64_t)f4.size() - 1; i >= 0; i--)  // build_fast4 emits children after their parent
+        for (int c = 0; c < 4; c++)
+          if (f4[i].child[c] >= 0) h[i] = std::max(h[i], 1 + h[f4[i].child[c]]);
+      group_by_height(h, forder, sc->f4_lvl);
+      if ((rc = upload(sc->f4_order, forder.data(), forder.size(), s))) return rc;
+    }
+  }
   const int n_global = plan.n_global;
   HIPC(hipStreamSynchronize(s));
   DScene& S = sc->S;
@@ -1228,6 +1246,93 @@ int rtx_scene_create(int device, const rtx_scene_desc* d, rtx_scene** out) {
 
 int rtx_scene_destroy(rtx_scene* s) {
   delete s;
+  return RTX_OK;
+}
+
+// ---- in-place updates ---------------------------------------------------------
+}  // extern "C"
+namespace {
+int update_range_ok(const rtx_scene* sc, int64_t first, int64_t count) {
+  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
+  if (first < 0 || count < 0 || first > sc->S.n_prims || count > sc->S.n_prims - first)
+    return fail(RTX_ERR_INVALID, "primitive range outside the scene");
+  return RTX_OK;
+}
+// Rewrite the records from one source (rtxrefit::UpdateArgs) and refit both trees, lowest height
+// first, all on `s`.  The range was checked by the caller.
+int update_and_refit(rtx_scene* sc, int64_t first, int64_t count, const rtx_prim* d_src, const double* d_g,
+                     hipStream_t s) {
+  rtxrefit::UpdateArgs a{};
+  a.prims = sc->prims.as<rtx_prim>();
+  a.tri_n = sc->tri_n.p ? sc->tri_n.as<double>() : nullptr;
+  a.ref_box = sc->n_nodes > 0 ? sc->ref_box.as<double>() : nullptr;
+  a.fast_box = sc->n_nodes > 0 ? sc->fast_box.as<float>() : nullptr;
+  a.first = first, a.count = count, a.src = d_src, a.src_g = d_g;
+  HIPC(rtxrefit::update_prims(a, s));
+  for (size_t k = 0; k + 1 < sc->node_lvl.size(); k++)
+    HIPC(rtxrefit::refit_nodes(sc->nodes.as<rtx_bvh_node>(), sc->ref_box.as<double>(),
+                               sc->node_order.as<uint32_t>() + sc->node_lvl[k], sc->node_lvl[k + 1] - sc->node_lvl[k], s));
+  for (size_t k = 0; k + 1 < sc->f4_lvl.size(); k++)
+    HIPC(rtxrefit::refit_f4(sc->fnodes.as<F4Node>(), sc->fast_box.as<float>(),
+                            sc->f4_order.as<uint32_t>() + sc->f4_lvl[k], sc->f4_lvl[k + 1] - sc->f4_lvl[k], s));
+  sc->epoch++;
+  return RTX_OK;
+}
+}  // namespace
+extern "C" {
+
+int rtx_scene_update_prims(rtx_scene* sc, int64_t first, int64_t count, const rtx_prim* prims) {
+  int rc;
+  if ((rc = update_range_ok(sc, first, count))) return rc;
+  if (count == 0) return RTX_OK;
+  if (!prims) return fail(RTX_ERR_INVALID, "prims is NULL");
+  for (int64_t i = 0; i < count; i++) {
+    const rtx_prim& p = prims[i];
+    if (p.kind != sc->kinds[(size_t)(first + i)]) return fail(RTX_ERR_INVALID, "an update may not change a primitive's kind");
+    if (p.material < 0 || p.material >= sc->n_materials) return fail(RTX_ERR_INVALID, "primitive material out of range");
+    const int used = p.kind == RTX_PRIM_SPHERE ? 4 : (p.kind == RTX_PRIM_TRIANGLE ? 9 : 5);
+    for (int k = 0; k < used; k++)
+      if (!std::isfinite(p.g[k])) return fail(RTX_ERR_INVALID, "primitive geometry is not finite");
+  }
+  HIPC(hipSetDevice(sc->device));
+  const size_t bytes = (size_t)count * sizeof(rtx_prim);
+  if ((rc = sc->upd_host.reserve(bytes))) return rc;
+  if ((rc = sc->upd_stage.reserve(bytes))) return rc;
+  std::memcpy(sc->upd_host.p, prims, bytes);
+  HIPC(hipMemcpyAsync(sc->upd_stage.p, sc->upd_host.p, bytes, hipMemcpyHostToDevice, sc->stream));
+  if ((rc = update_and_refit(sc, first, count, sc->upd_stage.as<rtx_prim>(), nullptr, sc->stream))) return rc;
+  HIPC(hipStreamSynchronize(sc->stream));  // the staging buffers are free again; a kernel failure shows here
+  return RTX_OK;
+}
+
+int rtx_scene_update_geometry_device(rtx_scene* sc, int64_t first, int64_t count, const double* d_g, void* stream) {
+  int rc;
+  if ((rc = update_range_ok(sc, first, count))) return rc;
+  if (count == 0) return RTX_OK;
+  if (!d_g) return fail(RTX_ERR_INVALID, "d_g is NULL");
+  HIPC(hipSetDevice(sc->device));
+  return update_and_refit(sc, first, count, nullptr, d_g, stream ? (hipStream_t)stream : sc->stream);
+}
+
+int rtx_scene_epoch(const rtx_scene* sc, int64_t* epoch) {
+  if (!sc || !epoch) return fail(RTX_ERR_INVALID, "NULL argument");
+  *epoch = sc->epoch;
+  return RTX_OK;
+}
+
+// Test hook (not in rtx.h): the device's reference-layout nodes (64 bytes each, at most
+// nodes_cap) and fast nodes (128 bytes each, at most f4_cap; none when the scene has no fast
+// tree) copied back to the host, after everything queued on the scene's stream.
+int rtx_internal_scene_trees(rtx_scene* sc, void* nodes_out, int64_t nodes_cap, void* f4_out, int64_t f4_cap) {
+  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
+  HIPC(hipSetDevice(sc->device));
+  const int64_t nn = std::min<int64_t>(std::max<int64_t>(0, nodes_cap), sc->n_nodes);
+  const int64_t nf = std::min<int64_t>(std::max<int64_t>(0, f4_cap), sc->fast_ok ? (int64_t)sc->n_f4 : 0);
+  if (nodes_out && nn)
+    HIPC(hipMemcpyAsync(nodes_out, sc->nodes.p, (size_t)nn * sizeof(rtx_bvh_node), hipMemcpyDeviceToHost, sc->stream));
+  if (f4_out && nf)
+    HIPC(hipMemcpyAsync(f4_out, sc->fnodes.p, (size_t)nf * sizeof(F4Node), hipMemcpyDeviceToHost, sc->stream));
+  HIPC(hipStreamSynchronize(sc->stream));
   return RTX_OK;
 }
 
@@ -1984,6 +2089,7 @@ int film_live(const rtx_film* f) {
   if (!f) return fail(RTX_ERR_INVALID, "film is NULL");
   if (!f->sc) return fail(RTX_ERR_INVALID, "the film's scene was destroyed");
   if (f->sc->device != f->device) return fail(RTX_ERR_INVALID, "the film's scene is on another device");
+  if (f->sc->epoch != f->epoch) return fail(RTX_ERR_INVALID, "scene changed since the film was created");
   return RTX_OK;
 }
 int film_sampler(const rtx_film* f) { return f->prm.mode == RTX_MODE_MEGAKERNEL ? 1 : 0; }
@@ -2031,6 +2137,7 @@ int rtx_film_create(rtx_scene* sc, const rtx_camera* cam, const rtx_render_param
   f->npix = subset_pixels(cam, prm, f->map, err);
   if (f->npix < 0) return fail(RTX_ERR_INVALID, err);
   f->sc = sc, f->device = sc->device, f->cam = *cam, f->prm = *prm;
+  f->epoch = sc->epoch;
   f->prm.spp = 0;
   f->prm.adaptive = prm->adaptive ? 1 : 0;
   HIPC(hipSetDevice(sc->device));
@@ -2077,6 +2184,19 @@ int rtx_film_destroy(rtx_film* f) {
 int rtx_film_samples(const rtx_film* f, int32_t* done) {
   if (!f || !done) return fail(RTX_ERR_INVALID, "NULL argument");
   *done = f->done;
+  return RTX_OK;
+}
+
+int rtx_film_reset(rtx_film* f) {
+  if (!f) return fail(RTX_ERR_INVALID, "film is NULL");
+  if (!f->sc) return fail(RTX_ERR_INVALID, "the film's scene was destroyed");
+  if (f->sc->device != f->device) return fail(RTX_ERR_INVALID, "the film's scene is on another device");
+  HIPC(hipSetDevice(f->device));
+  for (DevBuf* b : {&f->sum, &f->mean, &f->m2, &f->samples, &f->conv})
+    if (b->p) HIPC(hipMemsetAsync(b->p, 0, b->n, f->sc->stream));
+  f->done = 0;
+  f->aov_ready = false;
+  f->epoch = f->sc->epoch;
   return RTX_OK;
 }
 

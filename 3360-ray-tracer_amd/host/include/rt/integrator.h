@@ -43,6 +43,10 @@ class GpuRayIntegrator : public RayIntegrator {
   GpuRayIntegrator& operator=(const GpuRayIntegrator&) = delete;
   void IntersectBatch(const std::vector<core::Ray>& rays, std::vector<geom::HitRecord>& hits) const override;
   rtx_scene* device_scene() const { return dev_; }
+  // Replace primitives [first, first + prims.size()) of the device copy, in its own order (leaf
+  // order for a BVH world), and refit its trees in place (rtx_scene_update_prims): kinds stay,
+  // geometry must be finite.  flat() stays the description the copy was created from.  Throws std::runtime_error on a refused update.
+  void UpdatePrims(int64_t first, const std::vector<rtx_prim>& prims);
   const scene::FlatScene& flat() const { return flat_; }
   int device() const { return device_; }
   int precision() const { return precision_; }

@@ -8,6 +8,7 @@
 #include "rt/image.h"
 #include "rt/scene.h"
 #include "rtx.h"
+#include "rtx_bounds.h"
 
 struct rtx_host_scene {
   std::shared_ptr<rt::scene::Scene> root;
@@ -84,33 +85,31 @@ int rtx_host_scene_prim_indices(const rtx_host_scene* s, int32_t* out, int64_t n
 // (sphere.h, triangle.h:18-38, rect.h:42-45,87-89,132-134): the SAH builder's input.
 int rtx_prim_bounds(const rtx_prim* prims, int64_t n, double* out) {
   if ((!prims || !out) && n > 0) return host_fail(RTX_ERR_INVALID, "NULL argument");
-  using rt::core::Point3;
-  using rt::core::Vec3;
   for (int64_t i = 0; i < n; i++) {
     const rtx_prim& p = prims[i];
-    const double* g = p.g;
-    rt::geom::Aabb b;
-    if (p.kind == RTX_PRIM_SPHERE) {
-      const Vec3 rv(g[3], g[3], g[3]);
-      const Point3 c(g[0], g[1], g[2]);
-      b = rt::geom::Aabb(Point3(c + rv), Point3(c - rv));
-    } else if (p.kind == RTX_PRIM_TRIANGLE) {
-      Point3 mn(std::fmin(g[0], std::fmin(g[3], g[6])), std::fmin(g[1], std::fmin(g[4], g[7])),
-                std::fmin(g[2], std::fmin(g[5], g[8])));
-      Point3 mx(std::fmax(g[0], std::fmax(g[3], g[6])), std::fmax(g[1], std::fmax(g[4], g[7])),
-                std::fmax(g[2], std::fmax(g[5], g[8])));
-      const double eps = 1e-6f;
-      mn += -Vec3(eps, eps, eps);
-      mx += Vec3(eps, eps, eps);
-      b = rt::geom::Aabb(mn, mx);
-    } else if (p.kind >= RTX_PRIM_XY_RECT && p.kind <= RTX_PRIM_YZ_RECT) {
-      rt::geom::AxisRect r(p.kind, g[0], g[1], g[2], g[3], g[4], nullptr);
-      b = r.BoundingBox();
-    } else {
-      return host_fail(RTX_ERR_INVALID, "unknown primitive kind");
+    if (p.kind < RTX_PRIM_SPHERE || p.kind > RTX_PRIM_YZ_RECT) return host_fail(RTX_ERR_INVALID, "unknown primitive kind");
+    rtxb::ref_bounds(p.kind, p.g, out + 6 * i);  // rtx_bounds.h: the arithmetic the update kernel runs too
+  }
+  return RTX_OK;
+}
+
+// Bottom-up refit of reference-layout nodes over new primitive boxes, topology unchanged: what
+// rtx_scene_update_* does on the device (rtx_refit.hip), with the same routines (rtx_bounds.h).
+int rtx_bvh_refit_host(rtx_bvh_node* nodes, int64_t n_nodes, const double* bounds, int64_t n) {
+  if (n_nodes < 0 || n < 0) return host_fail(RTX_ERR_INVALID, "negative count");
+  if ((!nodes && n_nodes > 0) || (!bounds && n > 0)) return host_fail(RTX_ERR_INVALID, "NULL argument");
+  for (int64_t i = 0; i < n_nodes; i++) {
+    const rtx_bvh_node& q = nodes[i];
+    if (q.is_leaf) {
+      if ((int64_t)q.left_first + q.right_count > n) return host_fail(RTX_ERR_INVALID, "leaf range out of bounds");
+    } else if (q.left_first >= n_nodes || q.right_count >= n_nodes || q.left_first <= i || q.right_count <= i) {
+      return host_fail(RTX_ERR_INVALID, "child index out of bounds (nodes must be pre-order)");
     }
-    const double v[6] = {b.x.min_, b.y.min_, b.z.min_, b.x.max_, b.y.max_, b.z.max_};
-    std::memcpy(out + 6 * i, v, sizeof v);
+  }
+  for (int64_t i = n_nodes - 1; i >= 0; i--) {  // children come after their parent
+    rtx_bvh_node& q = nodes[i];
+    if (q.is_leaf) rtxb::refit_leaf(q, bounds);
+    else rtxb::refit_inner(q, nodes[q.left_first], nodes[q.right_count]);
   }
   return RTX_OK;
 }

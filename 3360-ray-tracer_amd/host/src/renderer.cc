@@ -24,6 +24,10 @@ GpuRayIntegrator::GpuRayIntegrator(const scene::Scene* world, int device, int pr
 
 GpuRayIntegrator::~GpuRayIntegrator() { rtx_scene_destroy(dev_); }
 
+void GpuRayIntegrator::UpdatePrims(int64_t first, const std::vector<rtx_prim>& prims) {
+  check(rtx_scene_update_prims(dev_, first, (int64_t)prims.size(), prims.data()), "rtx_scene_update_prims");
+}
+
 // cpu_ray_integrator.h:18-46 contract on the GPU: [0.001f, +inf), hit flag per record,
 // HitRecord::mat re-attached from the material id.
 void GpuRayIntegrator::IntersectBatch(const std::vector<core::Ray>& rays, std::vector<geom::HitRecord>& hits) const {

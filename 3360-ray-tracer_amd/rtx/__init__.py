@@ -132,7 +132,8 @@ EXPORTS = ["rtx_abi_version", "rtx_last_error", "rtx_device_count", "rtx_scene_c
            "rtx_film_create", "rtx_film_destroy", "rtx_film_render", "rtx_film_samples", "rtx_film_resolve",
            "rtx_film_resolve_device", "rtx_film_p3", "rtx_film_state_bytes", "rtx_film_save", "rtx_film_load",
            "rtx_film_blob_check", "rtx_denoise_params_default", "rtx_aov", "rtx_aov_device", "rtx_denoise",
-           "rtx_denoise_device", "rtx_film_denoise", "rtx_film_denoise_p3"]
+           "rtx_denoise_device", "rtx_film_denoise", "rtx_film_denoise_p3", "rtx_scene_update_prims",
+           "rtx_scene_update_geometry_device", "rtx_scene_epoch", "rtx_bvh_refit_host", "rtx_film_reset"]
 
 _lib = None
 
@@ -195,6 +196,11 @@ def lib():
             "rtx_denoise_device": ([vp, i32, i32, vp, vp, vp, vp, vp, C.POINTER(DenoiseParams), vp, vp], C.c_int),
             "rtx_film_denoise": ([vp, C.POINTER(DenoiseParams), vp], C.c_int),
             "rtx_film_denoise_p3": ([vp, C.POINTER(DenoiseParams), vp, sz, C.POINTER(sz)], C.c_int),
+            "rtx_scene_update_prims": ([vp, i64, i64, vp], C.c_int),
+            "rtx_scene_update_geometry_device": ([vp, i64, i64, vp, vp], C.c_int),
+            "rtx_scene_epoch": ([vp, C.POINTER(i64)], C.c_int),
+            "rtx_bvh_refit_host": ([vp, i64, vp, i64], C.c_int),
+            "rtx_film_reset": ([vp], C.c_int),
         }
         for name, (args, res) in sig.items():
             f = getattr(L, name)
@@ -314,6 +320,26 @@ class DeviceScene:
         if getattr(self, "h", None) and _lib is not None:
             _lib.rtx_scene_destroy(self.h)
             self.h = None
+
+    def update_prims(self, prims, first=0):
+        """Replace primitives [first, first + len(prims)) (PRIM_DTYPE, the scene's own order) and
+        refit both trees on the device (rtx_scene_update_prims).  Kinds must stay as they are."""
+        prims = np.ascontiguousarray(prims, dtype=PRIM_DTYPE)
+        _check(lib().rtx_scene_update_prims(self.h, first, len(prims), prims.ctypes.data_as(C.c_void_p)),
+               "rtx_scene_update_prims")
+
+    def update_geometry_device(self, ptr, first, count, stream=0):
+        """The same from device memory (rtx_scene_update_geometry_device): ptr names count x 9
+        doubles (e.g. a torch tensor's data_ptr()); kinds and materials are kept.  Asynchronous."""
+        _check(lib().rtx_scene_update_geometry_device(self.h, first, count, C.c_void_p(ptr),
+                                                      C.c_void_p(stream) if stream else None),
+               "rtx_scene_update_geometry_device")
+
+    def epoch(self):
+        """Updates applied to the scene so far (rtx_scene_epoch)."""
+        n = C.c_int64()
+        _check(lib().rtx_scene_epoch(self.h, C.byref(n)), "rtx_scene_epoch")
+        return n.value
 
     def film(self, cam, max_depth, seed=1234, adaptive=True, mode="wavefront", precision="parity", tile=None,
              stripes=None, samples_per_group=0, min_spp=16, rel_threshold=float(np.float32(0.05)), schedule=None,
@@ -447,6 +473,11 @@ class Film:
         st = Stats()
         _check(lib().rtx_film_render(self._handle(), budget, C.byref(st)), "rtx_film_render")
         return st.as_dict()
+
+    def reset(self):
+        """Zero the film and bind it to its scene's current epoch (rtx_film_reset): the way to go
+        on after the scene was updated."""
+        _check(lib().rtx_film_reset(self._handle()), "rtx_film_reset")
 
     @property
     def samples(self):
@@ -630,6 +661,16 @@ def bvh_build(bounds, device=0, on="gpu"):
     return nodes[:nn.value], idx[:n]
 
 
+def bvh_refit(nodes, bounds):
+    """Reference-layout nodes (NODE_DTYPE) refit bottom-up over (n, 6) primitive boxes in leaf
+    order, topology unchanged (rtx_bvh_refit_host; no device needed).  Returns a new array."""
+    nodes = np.ascontiguousarray(nodes, dtype=NODE_DTYPE).copy()
+    bounds = np.ascontiguousarray(bounds, dtype=np.float64).reshape(-1, 6)
+    _check(lib().rtx_bvh_refit_host(nodes.ctypes.data_as(C.c_void_p), len(nodes), bounds.ctypes.data_as(C.c_void_p),
+                                    len(bounds)), "rtx_bvh_refit_host")
+    return nodes
+
+
 def stripe_rows_of(height, stripe_rows, index, count, width=1):
     """Rows owned by stripe `index` (interleaved row stripes), in output order: the library's own
     pixel map (rtx_internal_stripe_rows: subset_pixels + PixelMap::xy, host side, no device)."""
@@ -669,6 +710,21 @@ def fast_tree(scene):
         _check(f(C.byref(d), info.ctypes.data_as(C.c_void_p), nodes.ctypes.data_as(C.c_void_p), len(nodes)),
                "rtx_internal_fast_tree")
     return {k: int(v) for k, v in zip(FAST_TREE_INFO, info)}, nodes
+
+
+def scene_trees(scene):
+    """Test hook (rtx_internal_scene_trees, not in rtx.h): the trees a DeviceScene holds on its
+    device right now, copied back: (reference-layout nodes NODE_DTYPE, fast nodes F4NODE_DTYPE;
+    the latter empty when the scene has no fast tree)."""
+    info, _ = fast_tree(scene.host)
+    f = lib().rtx_internal_scene_trees
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
+    f.restype = C.c_int
+    nodes = np.zeros(int(scene.host.desc().n_nodes), NODE_DTYPE)
+    f4 = np.zeros(info["n_f4"] if info["fast_ok"] else 0, F4NODE_DTYPE)
+    _check(f(scene.h, nodes.ctypes.data_as(C.c_void_p), len(nodes), f4.ctypes.data_as(C.c_void_p), len(f4)),
+           "rtx_internal_scene_trees")
+    return nodes, f4
 
 
 def write_ppm(path, rgb, width, height):

@@ -275,6 +275,30 @@ int rtx_device_count(int* n);
 int rtx_scene_create(int device, const rtx_scene_desc* desc, rtx_scene** out);
 int rtx_scene_destroy(rtx_scene* scene);
 
+/* ---- in-place updates of a live scene (DESIGN.md "Scene updates") ---------------------------
+ * Move or reshape primitives without re-creating the scene: the records are rewritten and both
+ * trees refit bottom-up over their unchanged topology, on the device.  The refit trees hold the
+ * bytes the host builders give for that topology, so hits and renders equal those of a scene
+ * created from the new primitives (apart from exact t ties, which depend on the topology).
+ * Primitive count, kinds, materials' table and textures stay; stack sizes and the persistent
+ * fast schedule are kept.  Tree quality degrades as geometry drifts from what the build saw:
+ * re-create the scene then. */
+/* Replace primitives [first, first + count) of the scene, in the scene's own order (leaf order
+ * when it has a BVH), and refit both trees over the unchanged topology.  prims[i].kind must equal
+ * the kind the scene holds at first + i; material may change (range-checked); geometry must be
+ * finite.  Checked on the host before any device work; on failure the scene is unchanged.
+ * count == 0: RTX_OK, nothing happens; a range outside the scene: RTX_ERR_INVALID. */
+int rtx_scene_update_prims(rtx_scene* scene, int64_t first, int64_t count, const rtx_prim* prims);
+/* Geometry only, from device memory: count x 9 doubles (rtx_prim.g), kinds and materials kept.
+ * Asynchronous on stream (NULL = the scene's stream).  Finite geometry is the caller's duty. */
+int rtx_scene_update_geometry_device(rtx_scene* scene, int64_t first, int64_t count, const double* d_g, void* stream);
+/* Updates applied to the scene so far (0 after rtx_scene_create). */
+int rtx_scene_epoch(const rtx_scene* scene, int64_t* epoch);
+/* Host-only: refit reference-layout nodes over n primitive boxes (n x 6 doubles, leaf order):
+ * leaves take the union of their primitives' boxes, internal nodes of their children.  Nodes
+ * must be pre-order (children after their parent) with leaf ranges inside n. */
+int rtx_bvh_refit_host(rtx_bvh_node* nodes, int64_t n_nodes, const double* bounds, int64_t n);
+
 /* Batch closest hit on [tmin, tmax); host buffers (PCIe round trip included). */
 int rtx_intersect(rtx_scene* scene, const rtx_ray* rays, size_t n, rtx_hit* hits, double tmin, double tmax,
                   int32_t precision);
@@ -395,6 +419,11 @@ int rtx_film_destroy(rtx_film* film);
  * NULL: then the call does not wait for the device) covers this call only. */
 int rtx_film_render(rtx_film* film, int32_t budget, rtx_stats* stats);
 int rtx_film_samples(const rtx_film* film, int32_t* done);
+/* A film remembers the scene's epoch (rtx_scene_epoch) it was created or last reset at; once the
+ * scene was updated, every film call except rtx_film_samples, rtx_film_destroy and this one
+ * returns RTX_ERR_INVALID ("scene changed since the film was created").
+ * Zero a film's pixel state and bind it to the scene's current epoch (drops its cached AOVs). */
+int rtx_film_reset(rtx_film* film);
 /* The film's output at its current budget, as rtx_render gives it (out_rgb 3 doubles per pixel
  * in subset order, out_spp may be NULL).  Host buffers. */
 int rtx_film_resolve(rtx_film* film, double* out_rgb, int32_t* out_spp);
