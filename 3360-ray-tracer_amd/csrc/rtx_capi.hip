@@ -1237,6 +1237,21 @@ int rtx_scene_create(int device, const rtx_scene_desc* d, rtx_scene** out) {
     if ((m.kind == RTX_MAT_LAMBERTIAN || m.kind == RTX_MAT_DIFFUSE_LIGHT) && m.texture >= 0) S.no_textures = 0;
   S.tree_kind = plan.tree_kind;  // the one kind of the tree's primitives (globals excluded)
   S.global[0] = global[0], S.global[1] = global[1];
+  // Plain global spheres (kGlobalSpheres, rtx_device.h): when every global is a sphere with
+  // radius > 0, fmax(0, radius) is the radius itself and radius * radius, the one product the
+  // test forms from the record alone, goes into the record's unused g[4], in the device's IEEE
+  // double multiplication.  An in-place update that reaches a global withdraws the flag
+  // (update_and_refit): the test then reads the record as any primitive's.
+  bool plain = S.n_global > 0;
+  for (int k = 0; k < S.n_global; k++) {
+    const rtx_prim& q = d->prims[global[k]];
+    plain = plain && q.kind == RTX_PRIM_SPHERE && q.g[3] > 0.0;
+  }
+  for (int k = 0; k < S.n_global && plain; k++) {
+    const double r = d->prims[global[k]].g[3], r2 = r * r;
+    HIPC(hipMemcpy(&sc->prims.as<rtx_prim>()[global[k]].g[4], &r2, sizeof r2, hipMemcpyHostToDevice));
+  }
+  if (plain) S.n_global |= rtxd::kGlobalSpheres;
   for (int64_t i = 0; i < d->n_prims && !S.has_tris; i++) S.has_tris = d->prims[i].kind == RTX_PRIM_TRIANGLE;
   if (S.use_bvh && d->nodes[0].is_leaf) S.froot_leaf = 1, S.froot_count = (int32_t)d->nodes[0].right_count;
   if (!d->nodes && d->n_nodes == 0) S.use_bvh = 0;
@@ -1268,6 +1283,9 @@ int update_and_refit(rtx_scene* sc, int64_t first, int64_t count, const rtx_prim
   a.ref_box = sc->n_nodes > 0 ? sc->ref_box.as<double>() : nullptr;
   a.fast_box = sc->n_nodes > 0 ? sc->fast_box.as<float>() : nullptr;
   a.first = first, a.count = count, a.src = d_src, a.src_g = d_g;
+  // a rewritten global is no longer known to be a plain sphere, nor is its g[4] its radius squared
+  for (int k = 0; k < (sc->S.n_global & 3); k++)
+    if (sc->S.global[k] >= first && sc->S.global[k] < first + count) sc->S.n_global &= 3;
   HIPC(rtxrefit::update_prims(a, s));
   for (size_t k = 0; k + 1 < sc->node_lvl.size(); k++)
     HIPC(rtxrefit::refit_nodes(sc->nodes.as<rtx_bvh_node>(), sc->ref_box.as<double>(),

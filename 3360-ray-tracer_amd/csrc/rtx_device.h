@@ -259,7 +259,10 @@ struct DScene {
   int32_t tree_kind;  // fast BVH: the one kind of every primitive in the tree, or -1
   int32_t all_lambertian;  // every material is a Lambertian
   int32_t no_textures;     // no material reads the texture table (solid colours resolved at upload)
-  int32_t n_global;   // fast BVH: primitives kept out of the tree, tested before every walk
+  // fast BVH: primitives kept out of the tree, tested before every walk.  Bits 0-1: their count
+  // (0..2); bit 2 (kGlobalSpheres): all of them are plain spheres (trav_globals).  Read the
+  // count as n_global & 3.
+  int32_t n_global;
   int32_t global[2];  // their indices into prims (see build_global_prims, rtx_capi.hip)
   const double* tri_n;  // per primitive (x, y, z, 0), a triangle's unit normal (nullptr: no triangles)
 };
@@ -805,9 +808,65 @@ __device__ __forceinline__ void trav_init(TravState& ts, double tmax) {
 // the converged control flow of the walk's start, instead of at scattered node visits where a
 // few lanes at a time would run them.  Testing a primitive earlier only tightens `closest`
 // sooner, so the closest hit is unchanged (up to the order of exact t ties, as for any tree).
-template <bool COUNT>
+//
+// Plain global spheres (DScene::n_global carries kGlobalSpheres: every global is a sphere with
+// radius > 0, decided at upload, rtx_scene_create): the record's address is the same for every
+// lane and every segment of the launch, so it is read with uniform loads (the constant address
+// space: the table is not written while a render kernel runs) into scalar registers that live
+// only for the test, and its g[4] holds radius * radius as the host formed it (fmax(0, radius)
+// is the radius itself).
+constexpr int32_t kGlobalSpheres = 4;  // flag bit of DScene::n_global beside the count (0..2)
+// Sphere::Hit's two roots with one division where the result allows it.  root1 = (h - sq) / a
+// and root2 = (h + sq) / a are tried in that order against (tmin, tmax).  With a positive and
+// finite and tmin >= 0: h - sq <= 0 (or NaN) gives root1 <= 0 (or NaN) whatever the rounding of
+// the quotient, so root1 fails tmin < root1 and the reference goes on to root2: dividing h + sq
+// alone decides the same and yields the same bits.  With h - sq > 0 the sequence is the
+// original one: root1, and root2 only for a lane whose root1 was out of range.  Every quotient
+// formed is one the original forms, from the same operands.  Any other a or tmin: the original
+// sequence.
+__device__ __forceinline__ bool sphere_root(double a, double h, double sq, double tmin, double tmax, double& root) {
+  const double n1 = h - sq;
+  const bool near_first = !(a > 0.0 && a < kInf && tmin >= 0.0) || n1 > 0.0;
+  root = (near_first ? n1 : h + sq) / a;
+  bool ok = tmin < root && root < tmax;
+  if (!ok && near_first) {
+    root = (h + sq) / a;
+    ok = tmin < root && root < tmax;
+  }
+  return ok;
+}
+// (SPHERES false: a build that keeps the generic test for plain spheres too, k_persistent)
+template <bool COUNT, bool SPHERES = true>
 __device__ __forceinline__ void trav_globals(const DScene& S, V3 o, V3 d, double tmin, Counters& cnt, TravState& ts) {
-  for (int i = 0; i < S.n_global; i++) {
+  if (SPHERES && (S.n_global & kGlobalSpheres)) {
+    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    typedef const __attribute__((address_space(4))) u4 cu4;
+    typedef const __attribute__((address_space(4))) d2 cd2;
+    for (int i = 0; i < (S.n_global & 3); i++) {
+      const uintptr_t P = (uintptr_t)(S.prims + (uint32_t)S.global[i]);
+      const u4 w0 = *(cu4*)P;  // kind, material, g[0]
+      const d2 w1 = *((cd2*)P + 1), w2 = *((cd2*)P + 2);
+      if (COUNT) {
+        cnt.prims++, cnt.sphs++;
+        if (first_active_lane()) cnt.wprims++;
+      }
+      // prim_t's sphere test on the record's centre and radius * radius
+      const V3 oc = V3{__hiloint2double((int)w0.w, (int)w0.z), w1.x, w1.y} - o;
+      const double a = len2(d);
+      const double h = dot(d, oc);
+      const double cc = len2(oc) - w2.y;
+      const double disc = h * h - a * cc;
+      double t;
+      if (!(disc < 0) && sphere_root(a, h, sqrt(disc), tmin, ts.closest, t))
+        ts.closest = t, ts.best = S.global[i], ts.mat = (int32_t)w0.y;
+    }
+    ts.tmax_f = f32_round_up(ts.closest);
+    return;
+  }
+  // (with SPHERES the flag bit is clear here and n_global is the count; a build without it comes
+  // here with the flag set and masks it)
+  for (int i = 0; i < (SPHERES ? S.n_global : (S.n_global & 3)); i++) {
     const uint32_t gi = (uint32_t)S.global[i];
     if (COUNT) {
       count_prim(cnt, S.prims + gi);

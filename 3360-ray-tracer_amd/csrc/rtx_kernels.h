@@ -564,7 +564,10 @@ __global__ __launch_bounds__(kBlock, kTraceWaves) void k_persistent(RenderArgs A
         const int active = __popcll(__ballot(1));  // lanes tracing this round
         if (!parked) {
           trav_init(trs, kInf);
-          trav_globals<COUNT>(A.S, P.o, P.d, tmin, c, trs);
+          // the leaf-step walk's Lambertian texture-free kind-specialised build spills more with
+          // the plain-sphere test (scratch 52 -> 84 B per lane, profiles/r07): it keeps the generic one
+          constexpr bool kGlobalSph = !(PARK == 1 && TK >= 0 && LAMB && NOTEX && MAP == 0);
+          trav_globals<COUNT, kGlobalSph>(A.S, P.o, P.d, tmin, c, trs);
         }
         // parking only when some lane of this round finishes first: every round makes progress
         // (the phase launches, MAP 1, run the same thresholds: leaf rounds at 6 / 12 lanes and

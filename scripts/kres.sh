@@ -8,7 +8,7 @@ else F="-mllvm -amdgpu-disable-clustered-low-occupancy-reschedule"; SRC=csrc/rtx
 OUT=$(mktemp /tmp/kres.XXXXXX.s)
 cd $R && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -I/root/repo/include \
   -Icsrc -Ihost/include $F "$@" --cuda-device-only -S $SRC -o $OUT 2>/dev/null || exit 1
-echo "kernel<STACK,FAST,COUNT,SCATTER,PARK,TK,LAMB,NOTEX,NODOF>  scratch_B sgpr vgpr vgpr_spill"
+echo "kernel<STACK,FAST,COUNT,SCATTER,PARK,TK,LAMB,NOTEX,NODOF,MAP>  scratch_B sgpr vgpr vgpr_spill"
 grep -A12 "\.name:.*k_persistent" $OUT | grep -E "\.name|private_segment|sgpr_count|vgpr_count|vgpr_spill" |
   paste - - - - - | awk '{print $2, $4, $6, $8, $10}' | sed 's/_ZN4rtxd12k_persistentI//; s/EEEvNS_10RenderArgsEPy//'
 echo "asm: $OUT"
