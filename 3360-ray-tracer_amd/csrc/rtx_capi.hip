@@ -23,6 +23,7 @@
 #include "rtx_denoise.h"
 #include "rtx_film.h"
 #include "rtx_frame_kernels.h"
+#include "rtx_occlusion.h"
 #include "rtx_p3.h"
 #include "rtx_scan.h"
 
@@ -239,6 +240,7 @@ struct rtx_scene {
   // render workspace (grow-only)
   DevBuf px_sum, px_mean, px_m2, px_samples, px_conv, lbuf, queue[2], counters, out_rgb, out_spp, rays, hits;
   DevBuf p3_scratch, p3_body;  // device P3 encoding (rtx_p3.h)
+  DevBuf occ;                  // rtx_occluded: the rays' bytes (the rays themselves stage through `rays`)
   DevBuf patch_q;              // adaptive early output: the pixels still sampling when it went
   // AOVs and the denoiser (rtx_denoise.h): the f64 AOVs of rtx_aov / a film's first denoise, the
   // host entry points' staged inputs, an adaptive film's variance, and the filter's f32 working
@@ -271,7 +273,7 @@ struct rtx_scene {
     for (DevBuf* b : {&nodes, &prims, &mats, &texs, &images, &fnodes, &tri_n, &px_sum, &px_mean, &px_m2, &px_samples,
                       &px_conv, &lbuf, &queue[0], &queue[1], &counters, &out_rgb, &out_spp, &rays, &hits, &p3_scratch,
                       &p3_body, &calib_rgb, &patch_q, &aov_f64, &dn_in, &dn_var, &dn_work[0], &dn_work[1], &dn_guide,
-                      &dn_alb})
+                      &dn_alb, &occ})
       b->release();
     for (auto& t : texels) t.release();
     stage_rgb.release(), stage_spp.release();
@@ -733,6 +735,52 @@ int aov_on(rtx_scene* sc, const rtx_camera* cam, const PixelMap& map, int64_t np
                             : launch_aov<64, true>(sc, cam, map, npix, d_albedo, d_normal, d_depth, s);
   return st == 32 ? launch_aov<32, false>(sc, cam, map, npix, d_albedo, d_normal, d_depth, s)
                   : launch_aov<64, false>(sc, cam, map, npix, d_albedo, d_normal, d_depth, s);
+}
+// ---- occlusion queries and the AO pass (rtx_occlusion.h): the walk is picked as in
+// rtx_intersect_device (fast only with a fast tree, the scene's stack size) ----
+template <int STACK, bool FAST>
+int launch_occluded(rtx_scene* sc, const rtx_ray* d_rays, int64_t n, uint8_t* d_out, double tmin, double tmax,
+                    hipStream_t s) {
+  hipLaunchKernelGGL((k_occluded<STACK, FAST>), dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock),
+                     stack_lds_bytes(STACK), s, sc->S, d_rays, n, d_out, tmin, tmax);
+  HIPC(hipGetLastError());
+  return RTX_OK;
+}
+// rays == nullptr: k_ao into d_out; else k_ao_rays (the test hook's sample rays)
+template <int STACK, bool FAST>
+int launch_ao(rtx_scene* sc, const rtx_camera* cam, const PixelMap& map, int64_t npix, const rtx_ao_params* ao,
+              double* d_out, rtx_ray* d_rays, hipStream_t s) {
+  const dim3 grid((unsigned)((npix + kBlock - 1) / kBlock));
+  if (d_rays)
+    hipLaunchKernelGGL((k_ao_rays<STACK, FAST>), grid, dim3(kBlock), stack_lds_bytes(STACK), s, sc->S, *cam, map, npix,
+                       ao->seed, ao->samples, d_rays);
+  else
+    hipLaunchKernelGGL((k_ao<STACK, FAST>), grid, dim3(kBlock), stack_lds_bytes(STACK), s, sc->S, *cam, map, npix,
+                       ao->seed, ao->samples, ao->radius, d_out);
+  HIPC(hipGetLastError());
+  return RTX_OK;
+}
+int ao_on(rtx_scene* sc, const rtx_camera* cam, const PixelMap& map, int64_t npix, int32_t precision,
+          const rtx_ao_params* ao, double* d_out, rtx_ray* d_rays, hipStream_t s) {
+  if (npix == 0) return RTX_OK;
+  const bool fast = precision == RTX_PREC_FAST && sc->fast_ok;
+  const int st = fast ? sc->stack_fast : sc->stack_parity;
+  if (fast) return st == 32 ? launch_ao<32, true>(sc, cam, map, npix, ao, d_out, d_rays, s)
+                            : launch_ao<64, true>(sc, cam, map, npix, ao, d_out, d_rays, s);
+  return st == 32 ? launch_ao<32, false>(sc, cam, map, npix, ao, d_out, d_rays, s)
+                  : launch_ao<64, false>(sc, cam, map, npix, ao, d_out, d_rays, s);
+}
+// the checks rtx_ao, rtx_ao_device and rtx_internal_ao_rays share; *npix: pixels of the subset
+int ao_check(const rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, const rtx_ao_params* ao,
+             PixelMap& map, int64_t* npix) {
+  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
+  if (!cam || !prm || !ao) return fail(RTX_ERR_INVALID, "NULL argument");
+  if (ao->samples < 1 || ao->samples > 1024) return fail(RTX_ERR_INVALID, "ao: samples outside 1..1024");
+  if (!(ao->radius > 0)) return fail(RTX_ERR_INVALID, "ao: radius must be positive");
+  std::string err;
+  *npix = subset_pixels(cam, prm, map, err);
+  if (*npix < 0) return fail(RTX_ERR_INVALID, err);
+  return RTX_OK;
 }
 int persistent_grid(rtx_scene* sc, const void* fn, size_t lds) {
   int per_cu = 0;
@@ -1383,6 +1431,87 @@ int rtx_intersect(rtx_scene* sc, const rtx_ray* rays, size_t n, rtx_hit* hits, d
                                  sc->stream)))
     return rc;
   HIPC(hipMemcpyAsync(hits, sc->hits.p, n * sizeof(rtx_hit), hipMemcpyDeviceToHost, sc->stream));
+  HIPC(hipStreamSynchronize(sc->stream));
+  return RTX_OK;
+}
+
+int rtx_occluded_device(rtx_scene* sc, const rtx_ray* d_rays, size_t n, uint8_t* d_out, double tmin, double tmax,
+                        int32_t precision, void* stream) {
+  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
+  if (!(tmin < tmax)) return fail(RTX_ERR_INVALID, "occluded: tmin must be below tmax");
+  if (n == 0) return RTX_OK;
+  if (!d_rays || !d_out) return fail(RTX_ERR_INVALID, "NULL buffer");
+  HIPC(hipSetDevice(sc->device));
+  hipStream_t s = stream ? (hipStream_t)stream : sc->stream;
+  const bool fast = precision == RTX_PREC_FAST && sc->fast_ok;
+  const int st = fast ? sc->stack_fast : sc->stack_parity;
+  if (fast) return st == 32 ? launch_occluded<32, true>(sc, d_rays, (int64_t)n, d_out, tmin, tmax, s)
+                            : launch_occluded<64, true>(sc, d_rays, (int64_t)n, d_out, tmin, tmax, s);
+  return st == 32 ? launch_occluded<32, false>(sc, d_rays, (int64_t)n, d_out, tmin, tmax, s)
+                  : launch_occluded<64, false>(sc, d_rays, (int64_t)n, d_out, tmin, tmax, s);
+}
+
+int rtx_occluded(rtx_scene* sc, const rtx_ray* rays, size_t n, uint8_t* out, double tmin, double tmax,
+                 int32_t precision) {
+  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
+  if (!(tmin < tmax)) return fail(RTX_ERR_INVALID, "occluded: tmin must be below tmax");
+  if (n == 0) return RTX_OK;
+  if (!rays || !out) return fail(RTX_ERR_INVALID, "NULL buffer");
+  HIPC(hipSetDevice(sc->device));
+  int rc;
+  if ((rc = sc->rays.reserve(n * sizeof(rtx_ray)))) return rc;
+  if ((rc = sc->occ.reserve(n))) return rc;
+  HIPC(hipMemcpyAsync(sc->rays.p, rays, n * sizeof(rtx_ray), hipMemcpyHostToDevice, sc->stream));
+  if ((rc = rtx_occluded_device(sc, sc->rays.as<rtx_ray>(), n, sc->occ.as<uint8_t>(), tmin, tmax, precision, sc->stream)))
+    return rc;
+  HIPC(hipMemcpyAsync(out, sc->occ.p, n, hipMemcpyDeviceToHost, sc->stream));
+  HIPC(hipStreamSynchronize(sc->stream));
+  return RTX_OK;
+}
+
+int rtx_ao_device(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, const rtx_ao_params* ao,
+                  double* d_out, void* stream) {
+  PixelMap map;
+  int64_t npix;
+  int rc;
+  if ((rc = ao_check(sc, cam, prm, ao, map, &npix))) return rc;
+  if (npix == 0) return RTX_OK;
+  if (!d_out) return fail(RTX_ERR_INVALID, "NULL buffer");
+  HIPC(hipSetDevice(sc->device));
+  return ao_on(sc, cam, map, npix, prm->precision, ao, d_out, nullptr, stream ? (hipStream_t)stream : sc->stream);
+}
+
+int rtx_ao(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, const rtx_ao_params* ao, double* out) {
+  PixelMap map;
+  int64_t npix;
+  int rc;
+  if ((rc = ao_check(sc, cam, prm, ao, map, &npix))) return rc;
+  if (npix == 0) return RTX_OK;
+  if (!out) return fail(RTX_ERR_INVALID, "NULL buffer");
+  HIPC(hipSetDevice(sc->device));
+  if ((rc = sc->aov_f64.reserve((size_t)npix * sizeof(double)))) return rc;  // (the AOV staging: one double per pixel)
+  if ((rc = ao_on(sc, cam, map, npix, prm->precision, ao, sc->aov_f64.as<double>(), nullptr, sc->stream))) return rc;
+  HIPC(hipMemcpyAsync(out, sc->aov_f64.p, (size_t)npix * sizeof(double), hipMemcpyDeviceToHost, sc->stream));
+  HIPC(hipStreamSynchronize(sc->stream));
+  return RTX_OK;
+}
+
+// Test hook (not in rtx.h): the sample rays of rtx_ao for the same arguments, npix * samples of
+// them, pixel major, made by the device function k_ao calls (ao_direction after ao_first_hit,
+// rtx_occlusion.h) and copied to the host; a pixel that misses has all-zero rays.
+extern "C" int rtx_internal_ao_rays(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm,
+                                    const rtx_ao_params* ao, rtx_ray* out) {
+  PixelMap map;
+  int64_t npix;
+  int rc;
+  if ((rc = ao_check(sc, cam, prm, ao, map, &npix))) return rc;
+  if (npix == 0) return RTX_OK;
+  if (!out) return fail(RTX_ERR_INVALID, "NULL buffer");
+  HIPC(hipSetDevice(sc->device));
+  const size_t bytes = (size_t)npix * (size_t)ao->samples * sizeof(rtx_ray);
+  if ((rc = sc->rays.reserve(bytes))) return rc;
+  if ((rc = ao_on(sc, cam, map, npix, prm->precision, ao, nullptr, sc->rays.as<rtx_ray>(), sc->stream))) return rc;
+  HIPC(hipMemcpyAsync(out, sc->rays.p, bytes, hipMemcpyDeviceToHost, sc->stream));
   HIPC(hipStreamSynchronize(sc->stream));
   return RTX_OK;
 }

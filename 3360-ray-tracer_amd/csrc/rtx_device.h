@@ -81,7 +81,9 @@ __device__ __forceinline__ V3 refract(V3 uv, V3 n, double eta) {                
 // Counter-based RNG: Philox-4x32-10, key (seed_lo, seed_hi ^ 0x52545831), counter
 // (draw >> 1, sample, global pixel, stream).  Stream 0 is the camera ray (GetRay); the
 // shading of path segment n (n = 0 for the primary hit) is stream n + 1, and `draw`
-// restarts at 0 in every stream.  Draw 2k of a stream is words 0/1 of block k, draw 2k+1
+// restarts at 0 in every stream; kRngStreamAo (below) is the ambient-occlusion pass's sample
+// directions (rtx_occlusion.h), above every segment's stream (n + 1 <= 2^31 for an int32
+// depth).  Draw 2k of a stream is words 0/1 of block k, draw 2k+1
 // words 2/3, as a 53-bit double.  Bit-identical to oracle/rtx_oracle.cc Rng::next (philox
 // mode).  A path's numbers depend only on (seed, pixel, sample, segment, draw): results
 // are independent of tiling, GPU count, queue order and scheduling.
@@ -91,6 +93,7 @@ __device__ __forceinline__ V3 refract(V3 uv, V3 n, double eta) {                
 // branch; a later block is computed where the wave first needs it, with per-lane counters,
 // so lanes at different draw positions still share one Philox evaluation.
 // ---------------------------------------------------------------------------------------
+constexpr uint32_t kRngStreamAo = 0xA0000000u;  // no render kernel opens it (streams 0 .. max_depth + 1)
 __device__ __forceinline__ void philox_block(uint32_t blk, uint32_t sample, uint32_t pixel, uint32_t stream,
                                              uint32_t k0, uint32_t k1, double& u0, double& u1) {
   uint32_t c0 = blk, c1 = sample, c2 = pixel, c3 = stream;

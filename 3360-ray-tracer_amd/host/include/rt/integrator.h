@@ -42,6 +42,12 @@ class GpuRayIntegrator : public RayIntegrator {
   GpuRayIntegrator(const GpuRayIntegrator&) = delete;
   GpuRayIntegrator& operator=(const GpuRayIntegrator&) = delete;
   void IntersectBatch(const std::vector<core::Ray>& rays, std::vector<geom::HitRecord>& hits) const override;
+  // Occlusion (any-hit) query beside IntersectBatch, on the same fixed tmin: out[i] = 1 iff some
+  // primitive is hit on (0.001f, tmax), i.e. iff IntersectBatch with that far end reports a hit
+  // (rtx_occluded: stops at the first primitive hit, one byte per ray).  Not part of the
+  // reference's RayIntegrator interface.
+  void OccludedBatch(const std::vector<core::Ray>& rays, std::vector<uint8_t>& out,
+                     double tmax = core::kInfinity) const;
   rtx_scene* device_scene() const { return dev_; }
   // Replace primitives [first, first + prims.size()) of the device copy, in its own order (leaf
   // order for a BVH world), and refit its trees in place (rtx_scene_update_prims): kinds stay,

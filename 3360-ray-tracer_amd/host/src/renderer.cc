@@ -55,6 +55,17 @@ void GpuRayIntegrator::IntersectBatch(const std::vector<core::Ray>& rays, std::v
   }
 }
 
+// Any-hit on (0.001f, tmax): out[i] = 1 iff IntersectBatch would set hits[i].hit with that far
+// end (rtx_occluded).  A segment a -> b: Ray(a, b - a), tmax 1.
+void GpuRayIntegrator::OccludedBatch(const std::vector<core::Ray>& rays, std::vector<uint8_t>& out, double tmax) const {
+  out.resize(rays.size());
+  if (rays.empty()) return;
+  std::vector<rtx_ray> r(rays.size());
+  for (size_t i = 0; i < rays.size(); i++)
+    for (int k = 0; k < 3; k++) r[i].origin[k] = rays[i].origin()[k], r[i].direction[k] = rays[i].direction()[k];
+  check(rtx_occluded(dev_, r.data(), r.size(), out.data(), RTX_SEAM_TMIN, tmax, precision_), "rtx_occluded");
+}
+
 }  // namespace rt::integrator
 
 namespace rt::renderer {

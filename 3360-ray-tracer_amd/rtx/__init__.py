@@ -122,6 +122,10 @@ class DenoiseParams(C.Structure):
                 ("sigma_depth", C.c_double), ("sigma_color", C.c_double)]
 
 
+class AoParams(C.Structure):
+    _fields_ = [("samples", C.c_int32), ("pad_", C.c_int32), ("radius", C.c_double), ("seed", C.c_uint64)]
+
+
 # Every entry point include/rtx.h declares (checked by tests/test_capi_exports.py).
 EXPORTS = ["rtx_abi_version", "rtx_last_error", "rtx_device_count", "rtx_scene_create", "rtx_scene_destroy",
            "rtx_intersect", "rtx_intersect_device", "rtx_camera_init", "rtx_render", "rtx_render_pixel_count",
@@ -133,7 +137,8 @@ EXPORTS = ["rtx_abi_version", "rtx_last_error", "rtx_device_count", "rtx_scene_c
            "rtx_film_resolve_device", "rtx_film_p3", "rtx_film_state_bytes", "rtx_film_save", "rtx_film_load",
            "rtx_film_blob_check", "rtx_denoise_params_default", "rtx_aov", "rtx_aov_device", "rtx_denoise",
            "rtx_denoise_device", "rtx_film_denoise", "rtx_film_denoise_p3", "rtx_scene_update_prims",
-           "rtx_scene_update_geometry_device", "rtx_scene_epoch", "rtx_bvh_refit_host", "rtx_film_reset"]
+           "rtx_scene_update_geometry_device", "rtx_scene_epoch", "rtx_bvh_refit_host", "rtx_film_reset",
+           "rtx_occluded", "rtx_occluded_device", "rtx_ao", "rtx_ao_device"]
 
 _lib = None
 
@@ -201,6 +206,10 @@ def lib():
             "rtx_scene_epoch": ([vp, C.POINTER(i64)], C.c_int),
             "rtx_bvh_refit_host": ([vp, i64, vp, i64], C.c_int),
             "rtx_film_reset": ([vp], C.c_int),
+            "rtx_occluded": ([vp, vp, sz, vp, dbl, dbl, i32], C.c_int),
+            "rtx_occluded_device": ([vp, vp, sz, vp, dbl, dbl, i32, vp], C.c_int),
+            "rtx_ao": ([vp, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(AoParams), vp], C.c_int),
+            "rtx_ao_device": ([vp, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(AoParams), vp, vp], C.c_int),
         }
         for name, (args, res) in sig.items():
             f = getattr(L, name)
@@ -365,6 +374,46 @@ class DeviceScene:
                                    hits.ctypes.data_as(C.c_void_p), tmin, tmax, PRECISIONS[precision]),
                "rtx_intersect")
         return hits
+
+    def occluded(self, rays, tmin=RTX_SEAM_TMIN, tmax=float("inf"), precision="parity"):
+        """Any-hit query (rtx_occluded): (n,) uint8, 1 where some primitive is hit on (tmin, tmax);
+        equals intersect(...)["hit"] != 0 for the same arguments.  A segment a -> b is origin a,
+        direction b - a, tmax 1."""
+        rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+        out = np.zeros(len(rays), np.uint8)
+        _check(lib().rtx_occluded(self.h, rays.ctypes.data_as(C.c_void_p), len(rays), out.ctypes.data_as(C.c_void_p),
+                                  tmin, tmax, PRECISIONS[precision]), "rtx_occluded")
+        return out
+
+    def occluded_device(self, d_rays, n, d_out, tmin=RTX_SEAM_TMIN, tmax=float("inf"), precision="parity", stream=0):
+        """The same on device buffers (rtx_occluded_device): d_rays names n x 6 doubles, d_out n
+        bytes (e.g. torch tensors' data_ptr()).  Asynchronous."""
+        _check(lib().rtx_occluded_device(self.h, C.c_void_p(d_rays), n, C.c_void_p(d_out), tmin, tmax,
+                                         PRECISIONS[precision], C.c_void_p(stream) if stream else None),
+               "rtx_occluded_device")
+
+    def _ao_args(self, cam, samples, radius, seed, tile, stripes, precision):
+        p = RenderParams()
+        p.precision = PRECISIONS[precision]
+        if stripes is not None:
+            p.stripe_rows, p.stripe_index, p.stripe_count = stripes
+        elif tile is not None:
+            p.x0, p.y0, p.w, p.h = tile
+        n = lib().rtx_render_pixel_count(C.byref(cam), C.byref(p))
+        if n < 0:
+            _check(n, "rtx_render_pixel_count")
+        a = AoParams()
+        a.samples, a.radius, a.seed = samples, radius, seed
+        return p, a, n
+
+    def ao(self, cam, samples=16, radius=1.0, seed=1234, tile=None, stripes=None, precision="parity"):
+        """Ambient occlusion of the pixel subset (rtx_ao), (n,) in subset order: the share of
+        `samples` cosine-weighted rays from each pixel's first hit that reach `radius` unoccluded
+        (1.0 where the pixel's ray misses)."""
+        p, a, n = self._ao_args(cam, samples, radius, seed, tile, stripes, precision)
+        out = np.zeros(n)
+        _check(lib().rtx_ao(self.h, C.byref(cam), C.byref(p), C.byref(a), out.ctypes.data_as(C.c_void_p)), "rtx_ao")
+        return out
 
     def aov(self, cam, tile=None, stripes=None, precision="parity"):
         """First-hit AOVs of the pixel subset (rtx_aov), in subset order: (albedo (n, 3), normal
@@ -562,6 +611,19 @@ def denoise(scene, rgb, albedo, normal, depth, width, height, variance=None, **o
     _check(lib().rtx_denoise(scene.h, width, height, *[a.ctypes.data_as(C.c_void_p) for a in arr],
                              None if var is None else var.ctypes.data_as(C.c_void_p),
                              C.byref(denoise_params(**over)), out.ctypes.data_as(C.c_void_p)), "rtx_denoise")
+    return out
+
+
+def ao_rays(scene, cam, samples=16, radius=1.0, seed=1234, tile=None, stripes=None, precision="parity"):
+    """Test hook (rtx_internal_ao_rays, not in rtx.h): the sample rays DeviceScene.ao traces for
+    the same arguments, (n, samples, 6), from the device function the AO kernel calls; all zero
+    for a pixel whose ray misses."""
+    p, a, n = scene._ao_args(cam, samples, radius, seed, tile, stripes, precision)
+    f = lib().rtx_internal_ao_rays
+    f.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(AoParams), C.c_void_p]
+    f.restype = C.c_int
+    out = np.zeros((n, samples, 6))
+    _check(f(scene.h, C.byref(cam), C.byref(p), C.byref(a), out.ctypes.data_as(C.c_void_p)), "rtx_internal_ao_rays")
     return out
 
 

@@ -3,7 +3,8 @@
 //             [--cameras cameras.json] [--spp N] [--depth N] [--seed S] [--fixed]
 //             [--mode wavefront|persistent|megakernel] [--precision parity|fast]
 //             [--mk-adaptive MIN:THRESHOLD] [--gpus N]
-//             [--chunks N] [--preview PREFIX] [--checkpoint FILE] [--resume FILE] [--denoise] > out.ppm
+//             [--chunks N] [--preview PREFIX] [--checkpoint FILE] [--resume FILE] [--denoise]
+//             [--ao N[,RADIUS]] > out.ppm
 // --gpus N renders one frame over N GPUs (interleaved row stripes, one host thread per GPU,
 // one gathered framebuffer and P3 output; identical pixels for every N); --devices 0,2,3
 // names the devices (a device may repeat: several streams on one GPU).
@@ -15,11 +16,16 @@
 // --denoise filters the PPM on stdout and every preview with the edge-avoiding denoiser at its
 // default parameters (first-hit albedo / normal / depth guides; an adaptive frame's own variance);
 // without it the bytes are those of the plain run.  Wavefront / persistent modes.
+// --ao N[,RADIUS] writes the ambient-occlusion pass instead of a render (rtx_ao: N cosine-weighted
+// any-hit rays of length RADIUS from each pixel's first hit; default RADIUS a quarter of the
+// scene's bounding-box diagonal) as a grey P3 PPM, AO replicated into R, G and B, through the
+// device encoder; --seed and --precision apply.  Without the flag no output changes.
 // --mk-adaptive selects the AdaptiveSampler (sampler.h:44-82) for --mode megakernel,
 // with max_samples = the preset's (or --spp) samples.
 // Defaults follow main.cc: preset "default" (fallback when unknown), the Cornell box
 // scene (switch(4), main.cc:178-183), WavefrontRenderer with the preset's maxDepth and
 // samplesPerPixel, adaptive sampling on; "Runtime: Xs" on stderr.
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -40,7 +46,8 @@ int main(int argc, char** argv) {
   uint64_t seed = 1234;
   bool fixed = false, denoise = false;
   std::vector<int> devices;
-  int mk_min = -1, gpus = 1, chunks = 0;
+  int mk_min = -1, gpus = 1, chunks = 0, ao_samples = 0;
+  double ao_radius = 0.0;  // 0: a quarter of the scene's bounding-box diagonal
   std::string preview, checkpoint, resume;
   float mk_thr = 0.0f;
   for (int i = 1; i < argc; i++) {
@@ -66,6 +73,16 @@ int main(int argc, char** argv) {
     else if (a == "--checkpoint") checkpoint = next();
     else if (a == "--resume") resume = next();
     else if (a == "--denoise") denoise = true;
+    else if (a == "--ao") {
+      const std::string v = next();
+      const size_t c = v.find(',');
+      ao_samples = std::atoi(v.substr(0, c).c_str());
+      if (c != std::string::npos) ao_radius = std::strtod(v.substr(c + 1).c_str(), nullptr);
+      if (ao_samples < 1 || ao_samples > 1024 || (c != std::string::npos && !(ao_radius > 0))) {
+        std::cerr << "--ao expects N[,RADIUS] with N in 1..1024 and RADIUS > 0\n";
+        return 2;
+      }
+    }
     else if (a == "--devices") {
       const std::string v = next();
       for (size_t p = 0; p < v.size();) {
@@ -120,7 +137,31 @@ int main(int argc, char** argv) {
       std::cerr << "--denoise needs --mode wavefront or persistent\n";
       return 2;
     }
-    if (mode == "megakernel") {
+    if (ao_samples > 0) {
+      integrator::GpuRayIntegrator integ(world.get(), devices.empty() ? 0 : devices[0],
+                                         precision == "fast" ? RTX_PREC_FAST : RTX_PREC_PARITY);
+      if (!(ao_radius > 0)) {
+        const geom::Aabb b = world->BoundingBox();
+        const double dx = b.x.max_ - b.x.min_, dy = b.y.max_ - b.y.min_, dz = b.z.max_ - b.z.min_;
+        ao_radius = 0.25 * std::sqrt(dx * dx + dy * dy + dz * dz);
+      }
+      const rtx_camera& dc = cam.device();
+      rtx_render_params whole{};
+      whole.precision = integ.precision();
+      const rtx_ao_params ap{ao_samples, 0, ao_radius, seed};
+      const size_t npix = (size_t)dc.image_width * (size_t)dc.image_height;
+      std::vector<double> ao(npix), rgb(3 * npix);
+      if (rtx_ao(integ.device_scene(), &dc, &whole, &ap, ao.data()) != RTX_OK)
+        throw std::runtime_error(std::string("rtx_ao: ") + rtx_last_error());
+      for (size_t i = 0; i < npix; i++) rgb[3 * i] = rgb[3 * i + 1] = rgb[3 * i + 2] = ao[i];
+      std::string bytes(rtx_p3_max_bytes(dc.image_width, dc.image_height), '\0');
+      size_t len = 0;
+      if (rtx_encode_p3(integ.device_scene(), rgb.data(), dc.image_width, dc.image_height, bytes.data(), bytes.size(),
+                        &len) != RTX_OK)
+        throw std::runtime_error(std::string("rtx_encode_p3: ") + rtx_last_error());
+      std::cout.write(bytes.data(), (std::streamsize)len);
+      std::clog << "AO: " << ao_samples << " samples, radius " << ao_radius << "\n";
+    } else if (mode == "megakernel") {
       integrator::DefaultSampler fixed_sampler(ns);
       integrator::AdaptiveSampler adaptive_sampler(mk_min, ns, mk_thr);
       integrator::Sampler& sampler = mk_min >= 0 ? (integrator::Sampler&)adaptive_sampler : fixed_sampler;

@@ -306,6 +306,19 @@ int rtx_intersect(rtx_scene* scene, const rtx_ray* rays, size_t n, rtx_hit* hits
 int rtx_intersect_device(rtx_scene* scene, const rtx_ray* d_rays, size_t n, rtx_hit* d_hits, double tmin,
                          double tmax, int32_t precision, void* stream);
 
+/* ---- occlusion (any-hit) queries (DESIGN.md "Occlusion queries and the AO pass") -------------
+ * Shadow, visibility and line-of-sight rays need one bit: is anything in the way?  The walk stops
+ * at the first primitive whose own test accepts the ray, keeps no closest distance, builds no
+ * record and writes one byte per ray. */
+/* 1 per ray if any primitive is hit on (tmin, tmax), else 0; equals rtx_intersect's hit flag for
+   the same arguments.  Directions are not normalised, so a segment a->b is origin a, direction
+   b - a, tmax 1.  tmin >= tmax (or a NaN) is RTX_ERR_INVALID.  Host buffers. */
+int rtx_occluded(rtx_scene* scene, const rtx_ray* rays, size_t n, uint8_t* out, double tmin, double tmax,
+                 int32_t precision);
+/* Device buffers; asynchronous on stream (NULL = the scene's stream). */
+int rtx_occluded_device(rtx_scene* scene, const rtx_ray* d_rays, size_t n, uint8_t* d_out, double tmin, double tmax,
+                        int32_t precision, void* stream);
+
 int rtx_camera_init(const rtx_camera_config* cfg, rtx_camera* out);
 
 /* Render the pixel subset selected by params.  out_rgb: linear sum/(float)samples, double,
@@ -456,6 +469,25 @@ int rtx_aov(rtx_scene* scene, const rtx_camera* cam, const rtx_render_params* pa
 /* Device buffers; stream is a hipStream_t (NULL = the scene's stream). */
 int rtx_aov_device(rtx_scene* scene, const rtx_camera* cam, const rtx_render_params* params, double* d_albedo,
                    double* d_normal, double* d_depth, void* stream);
+
+/* Ambient occlusion of the pixel subset of params (only the subset and `precision` are read), one
+ * double per pixel in subset order: from the first hit of the ray through the pixel's centre (the
+ * ray of rtx_aov), `samples` any-hit rays in unit cosine-weighted directions about the hit
+ * record's normal, each on (RTX_SEAM_TMIN, radius); out = unoccluded / samples, 1.0 where the
+ * pixel's ray misses.  One fused kernel: no ray goes through memory.  The directions come from a
+ * Philox stream of their own keyed by (seed, global pixel, sample), so a pixel's value does not
+ * depend on the subset.  samples outside 1..1024 or radius <= 0: RTX_ERR_INVALID. */
+typedef struct {
+  int32_t samples; /* 1..1024 */
+  int32_t pad_;
+  double radius;   /* > 0: the far end of every sample ray (directions are unit vectors) */
+  uint64_t seed;
+} rtx_ao_params;   /* 24 bytes */
+int rtx_ao(rtx_scene* scene, const rtx_camera* cam, const rtx_render_params* params, const rtx_ao_params* ao,
+           double* out);
+/* Device buffer; asynchronous on stream (NULL = the scene's stream). */
+int rtx_ao_device(rtx_scene* scene, const rtx_camera* cam, const rtx_render_params* params, const rtx_ao_params* ao,
+                  double* d_out, void* stream);
 
 enum { RTX_DENOISE_DEMODULATE = 1 }; /* filter colour / max(albedo, 1e-3), multiply back at the end */
 typedef struct {

@@ -52,6 +52,21 @@ class GpuRayIntegrator : public RayIntegrator {
     }
   }
 
+  // Occlusion (any-hit) query on the same fixed tmin: out[i] = 1 iff some primitive is hit on
+  // (0.001f, tmax), i.e. iff IntersectBatch with that far end would set hits[i].hit
+  // (rtx_occluded: stops at the first primitive hit, one byte per ray).  A segment a -> b is
+  // Ray(a, b - a) with tmax 1.  Not virtual: the reference's interface has no such call.
+  void OccludedBatch(const std::vector<core::Ray>& rays, std::vector<uint8_t>& out,
+                     double tmax = core::kInfinity) const {
+    out.resize(rays.size());
+    if (rays.empty()) return;
+    std::vector<rtx_ray> r(rays.size());
+    for (size_t i = 0; i < rays.size(); i++)
+      for (int k = 0; k < 3; k++) r[i].origin[k] = rays[i].origin()[k], r[i].direction[k] = rays[i].direction()[k];
+    if (rtx_occluded(dev_, r.data(), r.size(), out.data(), RTX_SEAM_TMIN, tmax, precision_) != RTX_OK)
+      throw std::runtime_error(std::string("rtx_occluded: ") + rtx_last_error());
+  }
+
   rtx_scene* device_scene() const { return dev_; }
   const RtxScene& flat() const { return flat_; }
 
