@@ -25,6 +25,7 @@
 #include "rtx_frame_kernels.h"
 #include "rtx_occlusion.h"
 #include "rtx_p3.h"
+#include "rtx_radiance.h"
 #include "rtx_scan.h"
 
 using namespace rtxd;
@@ -241,6 +242,11 @@ struct rtx_scene {
   DevBuf px_sum, px_mean, px_m2, px_samples, px_conv, lbuf, queue[2], counters, out_rgb, out_spp, rays, hits;
   DevBuf p3_scratch, p3_body;  // device P3 encoding (rtx_p3.h)
   DevBuf occ;                  // rtx_occluded: the rays' bytes (the rays themselves stage through `rays`)
+  // rtx_radiance: the slot scratch (radiance and segments per slot, the carry of a ray summed
+  // across chunks), and the host entry point's staging (pinned on the host; ids, output and
+  // segment totals on the device, the rays through `rays`)
+  DevBuf rad_L, rad_segs, rad_carry, rad_ids, rad_out, rad_oseg;
+  HostBuf rad_host;
   DevBuf patch_q;              // adaptive early output: the pixels still sampling when it went
   // AOVs and the denoiser (rtx_denoise.h): the f64 AOVs of rtx_aov / a film's first denoise, the
   // host entry points' staged inputs, an adaptive film's variance, and the filter's f32 working
@@ -273,8 +279,9 @@ struct rtx_scene {
     for (DevBuf* b : {&nodes, &prims, &mats, &texs, &images, &fnodes, &tri_n, &px_sum, &px_mean, &px_m2, &px_samples,
                       &px_conv, &lbuf, &queue[0], &queue[1], &counters, &out_rgb, &out_spp, &rays, &hits, &p3_scratch,
                       &p3_body, &calib_rgb, &patch_q, &aov_f64, &dn_in, &dn_var, &dn_work[0], &dn_work[1], &dn_guide,
-                      &dn_alb, &occ})
+                      &dn_alb, &occ, &rad_L, &rad_segs, &rad_carry, &rad_ids, &rad_out, &rad_oseg})
       b->release();
+    rad_host.release();
     for (auto& t : texels) t.release();
     stage_rgb.release(), stage_spp.release();
     for (auto& e : ev)
@@ -780,6 +787,71 @@ int ao_check(const rtx_scene* sc, const rtx_camera* cam, const rtx_render_params
   std::string err;
   *npix = subset_pixels(cam, prm, map, err);
   if (*npix < 0) return fail(RTX_ERR_INVALID, err);
+  return RTX_OK;
+}
+// ---- radiance queries (rtx_radiance.h): the walk is picked as in rtx_intersect_device ----
+// the slot cap of the calls that follow (rtx_internal_radiance_chunk; 0: kRadianceSlots)
+std::atomic<int64_t> g_radiance_chunk{0};
+template <int STACK, bool FAST>
+int launch_radiance(rtx_scene* sc, const RadianceChunk& A, hipStream_t s) {
+  hipLaunchKernelGGL((k_radiance<STACK, FAST>), dim3((A.slots + kBlock - 1) / kBlock), dim3(kBlock),
+                     stack_lds_bytes(STACK), s, sc->S, A);
+  HIPC(hipGetLastError());
+  return RTX_OK;
+}
+// the checks rtx_radiance and rtx_radiance_device share, in the documented order
+int radiance_check(const rtx_scene* sc, const rtx_radiance_params* prm, const void* rays, const void* out) {
+  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
+  if (!prm) return fail(RTX_ERR_INVALID, "NULL argument");
+  if (!rays || !out) return fail(RTX_ERR_INVALID, "NULL buffer");
+  if (prm->spp < 1) return fail(RTX_ERR_INVALID, "radiance: spp must be at least 1");
+  if (prm->first_sample < 0 || prm->first_sample > 0x7FFFFFFF - prm->spp)
+    return fail(RTX_ERR_INVALID, "radiance: first_sample must be >= 0 and first_sample + spp fit int32");
+  if (prm->max_depth < 0) return fail(RTX_ERR_INVALID, "negative max_depth");
+  if (prm->precision != RTX_PREC_PARITY && prm->precision != RTX_PREC_FAST)
+    return fail(RTX_ERR_INVALID, "radiance: bad precision");
+  return RTX_OK;
+}
+// n > 0 rays on device buffers, in chunks of at most `cap` slots (ray x sample): whole rays per
+// chunk, or, when one ray's samples exceed the cap, one ray at a time in runs of `cap` samples
+// whose partial sum k_radiance_sum carries.  id_base: the pixel key of d_rays[0] when d_ids is
+// null (the host entry point's batches).
+int radiance_on(rtx_scene* sc, const rtx_ray* d_rays, const uint32_t* d_ids, uint64_t id_base, int64_t n,
+                const rtx_radiance_params* prm, double* d_out, uint32_t* d_segs, hipStream_t s) {
+  const int64_t tuned = g_radiance_chunk.load();
+  const int64_t cap = std::min<int64_t>(tuned > 0 ? tuned : kRadianceSlots, kRadianceSlotsMax);
+  const int64_t spp = prm->spp;
+  const int64_t rays_per = std::max<int64_t>(1, cap / spp);  // rays per chunk
+  const int64_t k_per = std::min<int64_t>(spp, cap);         // samples of a ray per chunk
+  const int64_t most = std::min<int64_t>(n, rays_per) * k_per;  // slots of the largest chunk (<= cap)
+  int rc;
+  if ((rc = sc->rad_L.reserve((size_t)most * 3 * sizeof(double)))) return rc;
+  if ((rc = sc->rad_segs.reserve((size_t)most * sizeof(uint32_t)))) return rc;
+  if (k_per < spp) {  // (one ray per chunk)
+    if ((rc = sc->rad_carry.reserve(4 * sizeof(double)))) return rc;
+  }
+  const bool fast = prm->precision == RTX_PREC_FAST && sc->fast_ok;
+  const int st = fast ? sc->stack_fast : sc->stack_parity;
+  double* const carry = k_per < spp ? sc->rad_carry.as<double>() : nullptr;
+  for (int64_t r0 = 0; r0 < n; r0 += rays_per) {
+    const int64_t nr = std::min<int64_t>(rays_per, n - r0);
+    for (int64_t k0 = 0; k0 < spp; k0 += k_per) {
+      const int64_t K = std::min<int64_t>(k_per, spp - k0);
+      RadianceChunk A;
+      A.rays = d_rays, A.ids = d_ids, A.ray0 = r0, A.id_base = id_base;
+      A.slots = (uint32_t)(nr * K), A.K = (uint32_t)K;
+      A.s0 = (int32_t)(prm->first_sample + k0), A.max_depth = prm->max_depth, A.seed = prm->seed;
+      A.L = sc->rad_L.as<double>(), A.segs = sc->rad_segs.as<uint32_t>();
+      if (fast) rc = st == 32 ? launch_radiance<32, true>(sc, A, s) : launch_radiance<64, true>(sc, A, s);
+      else rc = st == 32 ? launch_radiance<32, false>(sc, A, s) : launch_radiance<64, false>(sc, A, s);
+      if (rc) return rc;
+      hipLaunchKernelGGL(k_radiance_sum, dim3((unsigned)((nr + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
+                         sc->rad_L.as<double>(), sc->rad_segs.as<uint32_t>(), nr, (uint32_t)K, k0 == 0 ? 1 : 0,
+                         k0 + K == spp ? 1 : 0, prm->spp, carry, carry ? (uint32_t*)(carry + 3) : nullptr,
+                         d_out + 3 * r0, d_segs ? d_segs + r0 : nullptr);
+      HIPC(hipGetLastError());
+    }
+  }
   return RTX_OK;
 }
 int persistent_grid(rtx_scene* sc, const void* fn, size_t lds) {
@@ -1511,6 +1583,96 @@ extern "C" int rtx_internal_ao_rays(rtx_scene* sc, const rtx_camera* cam, const 
   const size_t bytes = (size_t)npix * (size_t)ao->samples * sizeof(rtx_ray);
   if ((rc = sc->rays.reserve(bytes))) return rc;
   if ((rc = ao_on(sc, cam, map, npix, prm->precision, ao, nullptr, sc->rays.as<rtx_ray>(), sc->stream))) return rc;
+  HIPC(hipMemcpyAsync(out, sc->rays.p, bytes, hipMemcpyDeviceToHost, sc->stream));
+  HIPC(hipStreamSynchronize(sc->stream));
+  return RTX_OK;
+}
+
+int rtx_radiance_device(rtx_scene* sc, const rtx_ray* d_rays, const uint32_t* d_ids, size_t n,
+                        const rtx_radiance_params* prm, double* d_out_rgb, uint32_t* d_out_segments, void* stream) {
+  int rc;
+  if ((rc = radiance_check(sc, prm, d_rays, d_out_rgb))) return rc;
+  if (n == 0) return RTX_OK;
+  HIPC(hipSetDevice(sc->device));
+  return radiance_on(sc, d_rays, d_ids, 0, (int64_t)n, prm, d_out_rgb, d_out_segments,
+                     stream ? (hipStream_t)stream : sc->stream);
+}
+
+// The host entry point works in batches of kRadianceHostRays rays: the caller's rays and ids are
+// copied into pinned memory, traced, and the results copied back out of it.
+constexpr size_t kRadianceHostRays = (size_t)1 << 20;
+int rtx_radiance(rtx_scene* sc, const rtx_ray* rays, const uint32_t* ids, size_t n, const rtx_radiance_params* prm,
+                 double* out_rgb, uint32_t* out_segments) {
+  int rc;
+  if ((rc = radiance_check(sc, prm, rays, out_rgb))) return rc;
+  if (n == 0) return RTX_OK;
+  HIPC(hipSetDevice(sc->device));
+  const size_t m = std::min(n, kRadianceHostRays);
+  // pinned: rays | rgb | ids | segments (8-byte items first)
+  const size_t off_rgb = m * sizeof(rtx_ray), off_ids = off_rgb + m * 3 * sizeof(double),
+               off_seg = off_ids + m * sizeof(uint32_t);
+  if ((rc = sc->rad_host.reserve(off_seg + m * sizeof(uint32_t)))) return rc;
+  if ((rc = sc->rays.reserve(m * sizeof(rtx_ray)))) return rc;
+  if ((rc = sc->rad_out.reserve(m * 3 * sizeof(double)))) return rc;
+  if ((rc = sc->rad_oseg.reserve(m * sizeof(uint32_t)))) return rc;
+  if (ids && (rc = sc->rad_ids.reserve(m * sizeof(uint32_t)))) return rc;
+  char* const pin = (char*)sc->rad_host.p;
+  for (size_t b0 = 0; b0 < n; b0 += m) {
+    const size_t nb = std::min(m, n - b0);
+    std::memcpy(pin, rays + b0, nb * sizeof(rtx_ray));
+    HIPC(hipMemcpyAsync(sc->rays.p, pin, nb * sizeof(rtx_ray), hipMemcpyHostToDevice, sc->stream));
+    if (ids) {
+      std::memcpy(pin + off_ids, ids + b0, nb * sizeof(uint32_t));
+      HIPC(hipMemcpyAsync(sc->rad_ids.p, pin + off_ids, nb * sizeof(uint32_t), hipMemcpyHostToDevice, sc->stream));
+    }
+    if ((rc = radiance_on(sc, sc->rays.as<rtx_ray>(), ids ? sc->rad_ids.as<uint32_t>() : nullptr, (uint64_t)b0,
+                          (int64_t)nb, prm, sc->rad_out.as<double>(), sc->rad_oseg.as<uint32_t>(), sc->stream)))
+      return rc;
+    HIPC(hipMemcpyAsync(pin + off_rgb, sc->rad_out.p, nb * 3 * sizeof(double), hipMemcpyDeviceToHost, sc->stream));
+    if (out_segments)
+      HIPC(hipMemcpyAsync(pin + off_seg, sc->rad_oseg.p, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, sc->stream));
+    HIPC(hipStreamSynchronize(sc->stream));
+    std::memcpy(out_rgb + 3 * b0, pin + off_rgb, nb * 3 * sizeof(double));
+    if (out_segments) std::memcpy(out_segments + b0, pin + off_seg, nb * sizeof(uint32_t));
+  }
+  return RTX_OK;
+}
+
+// Test hook (not in rtx.h): the slot cap of the radiance calls that follow in this process
+// (0 restores kRadianceSlots), so chunk seams are reached at small shapes.  Results never
+// depend on it.
+extern "C" int rtx_internal_radiance_chunk(int64_t slots) {
+  if (slots < 0) return fail(RTX_ERR_INVALID, "radiance chunk: negative slot count");
+  g_radiance_chunk.store(slots);
+  return RTX_OK;
+}
+
+// Test hook (not in rtx.h): the primary rays the render kernels generate for the pixel subset of
+// prm (its subset and seed are read), samples [first_sample, first_sample + spp) of each pixel:
+// npix x spp x 6 doubles (origin, direction), pixel major, from get_ray with
+// make_rng(seed, global pixel, sample, 0) as k_wf_generate calls it.
+extern "C" int rtx_internal_camera_rays(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm,
+                                        int32_t first_sample, int32_t spp, double* out) {
+  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
+  if (!cam || !prm) return fail(RTX_ERR_INVALID, "NULL argument");
+  if (!out) return fail(RTX_ERR_INVALID, "NULL buffer");
+  if (spp < 1) return fail(RTX_ERR_INVALID, "camera rays: spp must be at least 1");
+  if (first_sample < 0 || first_sample > 0x7FFFFFFF - spp)
+    return fail(RTX_ERR_INVALID, "camera rays: first_sample must be >= 0 and first_sample + spp fit int32");
+  PixelMap map;
+  std::string err;
+  const int64_t npix = subset_pixels(cam, prm, map, err);
+  if (npix < 0) return fail(RTX_ERR_INVALID, err);
+  if (npix == 0) return RTX_OK;
+  if (npix * (int64_t)spp > kRadianceSlotsMax) return fail(RTX_ERR_INVALID, "camera rays: too many rays for one call");
+  HIPC(hipSetDevice(sc->device));
+  const uint32_t nslots = (uint32_t)(npix * spp);
+  const size_t bytes = (size_t)nslots * 6 * sizeof(double);
+  int rc;
+  if ((rc = sc->rays.reserve(bytes))) return rc;
+  hipLaunchKernelGGL(k_camera_rays, dim3((nslots + kBlock - 1) / kBlock), dim3(kBlock), 0, sc->stream, *cam, map, nslots,
+                     (uint32_t)spp, prm->seed, first_sample, sc->rays.as<double>());
+  HIPC(hipGetLastError());
   HIPC(hipMemcpyAsync(out, sc->rays.p, bytes, hipMemcpyDeviceToHost, sc->stream));
   HIPC(hipStreamSynchronize(sc->stream));
   return RTX_OK;

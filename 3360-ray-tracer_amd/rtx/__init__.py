@@ -126,6 +126,11 @@ class AoParams(C.Structure):
     _fields_ = [("samples", C.c_int32), ("pad_", C.c_int32), ("radius", C.c_double), ("seed", C.c_uint64)]
 
 
+class RadianceParams(C.Structure):
+    _fields_ = [("spp", C.c_int32), ("max_depth", C.c_int32), ("first_sample", C.c_int32), ("precision", C.c_int32),
+                ("seed", C.c_uint64)]
+
+
 # Every entry point include/rtx.h declares (checked by tests/test_capi_exports.py).
 EXPORTS = ["rtx_abi_version", "rtx_last_error", "rtx_device_count", "rtx_scene_create", "rtx_scene_destroy",
            "rtx_intersect", "rtx_intersect_device", "rtx_camera_init", "rtx_render", "rtx_render_pixel_count",
@@ -138,7 +143,7 @@ EXPORTS = ["rtx_abi_version", "rtx_last_error", "rtx_device_count", "rtx_scene_c
            "rtx_film_blob_check", "rtx_denoise_params_default", "rtx_aov", "rtx_aov_device", "rtx_denoise",
            "rtx_denoise_device", "rtx_film_denoise", "rtx_film_denoise_p3", "rtx_scene_update_prims",
            "rtx_scene_update_geometry_device", "rtx_scene_epoch", "rtx_bvh_refit_host", "rtx_film_reset",
-           "rtx_occluded", "rtx_occluded_device", "rtx_ao", "rtx_ao_device"]
+           "rtx_occluded", "rtx_occluded_device", "rtx_ao", "rtx_ao_device", "rtx_radiance", "rtx_radiance_device"]
 
 _lib = None
 
@@ -210,6 +215,8 @@ def lib():
             "rtx_occluded_device": ([vp, vp, sz, vp, dbl, dbl, i32, vp], C.c_int),
             "rtx_ao": ([vp, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(AoParams), vp], C.c_int),
             "rtx_ao_device": ([vp, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(AoParams), vp, vp], C.c_int),
+            "rtx_radiance": ([vp, vp, vp, sz, C.POINTER(RadianceParams), vp, vp], C.c_int),
+            "rtx_radiance_device": ([vp, vp, vp, sz, C.POINTER(RadianceParams), vp, vp, vp], C.c_int),
         }
         for name, (args, res) in sig.items():
             f = getattr(L, name)
@@ -391,6 +398,43 @@ class DeviceScene:
         _check(lib().rtx_occluded_device(self.h, C.c_void_p(d_rays), n, C.c_void_p(d_out), tmin, tmax,
                                          PRECISIONS[precision], C.c_void_p(stream) if stream else None),
                "rtx_occluded_device")
+
+    @staticmethod
+    def _radiance_params(spp, max_depth, seed, first_sample, precision):
+        p = RadianceParams()
+        p.spp, p.max_depth, p.first_sample, p.precision, p.seed = spp, max_depth, first_sample, PRECISIONS[precision], seed
+        return p
+
+    def radiance(self, rays, spp, max_depth, seed=1234, ids=None, first_sample=0, precision="parity", segments=False):
+        """Radiance query (rtx_radiance): (n, 3), the mean of `spp` paths started from each ray as
+        its depth-0 segment, traced and shaded as render(mode="wavefront", adaptive=False) does.
+        Path i, k draws from (seed, pixel = ids[i] or i, sample = first_sample + k), so the primary
+        rays of a pixel with its global index give that pixel's render value.  segments=True: also
+        the (n,) uint32 segments traced per ray."""
+        rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+        n = len(rays)
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+            if len(ids) != n:
+                raise ValueError("radiance: one id per ray")
+        out = np.zeros((n, 3))
+        segs = np.zeros(n, np.uint32) if segments else None
+        p = self._radiance_params(spp, max_depth, seed, first_sample, precision)
+        _check(lib().rtx_radiance(self.h, rays.ctypes.data_as(C.c_void_p),
+                                  None if ids is None else ids.ctypes.data_as(C.c_void_p), n, C.byref(p),
+                                  out.ctypes.data_as(C.c_void_p),
+                                  None if segs is None else segs.ctypes.data_as(C.c_void_p)), "rtx_radiance")
+        return (out, segs) if segments else out
+
+    def radiance_device(self, d_rays, n, d_out, spp, max_depth, seed=1234, first_sample=0, precision="parity",
+                        d_ids=0, d_segments=0, stream=0):
+        """The same on device buffers (rtx_radiance_device): d_rays names n x 6 doubles, d_out
+        n x 3 doubles, d_ids n uint32 (0: the ray's index), d_segments n uint32 (0: none), e.g.
+        torch tensors' data_ptr().  Asynchronous."""
+        p = self._radiance_params(spp, max_depth, seed, first_sample, precision)
+        _check(lib().rtx_radiance_device(self.h, C.c_void_p(d_rays), C.c_void_p(d_ids) if d_ids else None, n,
+                                         C.byref(p), C.c_void_p(d_out), C.c_void_p(d_segments) if d_segments else None,
+                                         C.c_void_p(stream) if stream else None), "rtx_radiance_device")
 
     def _ao_args(self, cam, samples, radius, seed, tile, stripes, precision):
         p = RenderParams()
@@ -625,6 +669,38 @@ def ao_rays(scene, cam, samples=16, radius=1.0, seed=1234, tile=None, stripes=No
     out = np.zeros((n, samples, 6))
     _check(f(scene.h, C.byref(cam), C.byref(p), C.byref(a), out.ctypes.data_as(C.c_void_p)), "rtx_internal_ao_rays")
     return out
+
+
+def camera_rays(scene, cam, spp, seed=1234, first_sample=0, tile=None, stripes=None):
+    """Test hook (rtx_internal_camera_rays, not in rtx.h): the primary rays the render kernels
+    generate for samples [first_sample, first_sample + spp) of the pixel subset, (n, spp, 6) in
+    subset order, from the device function they call."""
+    p = RenderParams()
+    p.seed = seed
+    if stripes is not None:
+        p.stripe_rows, p.stripe_index, p.stripe_count = stripes
+    elif tile is not None:
+        p.x0, p.y0, p.w, p.h = tile
+    n = lib().rtx_render_pixel_count(C.byref(cam), C.byref(p))
+    if n < 0:
+        _check(n, "rtx_render_pixel_count")
+    f = lib().rtx_internal_camera_rays
+    f.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_int32, C.c_int32, C.c_void_p]
+    f.restype = C.c_int
+    out = np.zeros((n, spp, 6))
+    _check(f(scene.h, C.byref(cam), C.byref(p), first_sample, spp, out.ctypes.data_as(C.c_void_p)),
+           "rtx_internal_camera_rays")
+    return out
+
+
+def radiance_chunk(slots=0):
+    """Test hook (rtx_internal_radiance_chunk, not in rtx.h): the slot cap (ray x sample) of the
+    radiance calls that follow in this process; 0 restores the default.  Results never depend on
+    it, only the chunking does."""
+    f = lib().rtx_internal_radiance_chunk
+    f.argtypes = [C.c_int64]
+    f.restype = C.c_int
+    _check(f(slots), "rtx_internal_radiance_chunk")
 
 
 def adapt_tune(phase_slots=0, phase_kcap=0, first_map=-1, phase_mstep=-1.0, margin1=-1.0, pool_w=-1.0):

@@ -489,6 +489,35 @@ int rtx_ao(rtx_scene* scene, const rtx_camera* cam, const rtx_render_params* par
 int rtx_ao_device(rtx_scene* scene, const rtx_camera* cam, const rtx_render_params* params, const rtx_ao_params* ao,
                   double* d_out, void* stream);
 
+/* ---- radiance queries (DESIGN.md "Radiance queries") -----------------------------------------
+ * How much light arrives along these rays?  The bounce loop of rtx_render (RTX_MODE_WAVEFRONT
+ * semantics, fixed sampling) started from rays the caller supplies instead of the built-in
+ * camera: for ray i and sample k in [0, spp) a path starts with rays[i] as its depth-0 segment
+ * and throughput 1; its random numbers are keyed by (seed, pixel = ids ? ids[i] : (uint32_t)i,
+ * sample = first_sample + k), segment d shading from stream d + 1 (stream 0, the camera's, is
+ * never opened).  Every segment takes the closest hit on (RTX_SEAM_TMIN, +inf), with the walk
+ * rtx_intersect_device picks for `precision`; paths end as a render's do (sky on a miss, emitters,
+ * absorption, max_depth, Russian roulette past depth 5).  So from the primary rays of a pixel, its
+ * global index and the sample indices, the query returns exactly what rtx_render accumulates.
+ * out_rgb: 3 doubles per ray, the in-order sum of the spp radiances times 1 / (double)(float)spp
+ * (the fixed-spp resolve).  out_segments (may be NULL): segments traced for the ray over all its
+ * samples.  The live scene is read (after rtx_scene_update_* the new geometry); no film is
+ * involved.  Non-finite rays are the caller's duty.  One call at a time per scene. */
+typedef struct {
+  int32_t spp;          /* samples per ray, >= 1 */
+  int32_t max_depth;    /* as rtx_render_params.max_depth (>= 0) */
+  int32_t first_sample; /* RNG sample index of the first sample, >= 0; first_sample + spp must fit int32 */
+  int32_t precision;    /* RTX_PREC_* */
+  uint64_t seed;
+} rtx_radiance_params;  /* 24 bytes */
+/* Host buffers, staged through pinned memory; returns when out_rgb / out_segments are written. */
+int rtx_radiance(rtx_scene* scene, const rtx_ray* rays, const uint32_t* ids, size_t n,
+                 const rtx_radiance_params* params, double* out_rgb, uint32_t* out_segments);
+/* Device buffers; asynchronous on stream (NULL = the scene's stream). */
+int rtx_radiance_device(rtx_scene* scene, const rtx_ray* d_rays, const uint32_t* d_ids, size_t n,
+                        const rtx_radiance_params* params, double* d_out_rgb, uint32_t* d_out_segments,
+                        void* stream);
+
 enum { RTX_DENOISE_DEMODULATE = 1 }; /* filter colour / max(albedo, 1e-3), multiply back at the end */
 typedef struct {
   int32_t iterations; /* 0..8; iteration k filters 5 x 5 taps at step 2^k; 0 copies the input */

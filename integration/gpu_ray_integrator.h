@@ -67,6 +67,29 @@ class GpuRayIntegrator : public RayIntegrator {
       throw std::runtime_error(std::string("rtx_occluded: ") + rtx_last_error());
   }
 
+  // Radiance query: out[i] = the mean of spp paths started from rays[i] as their depth-0 segment
+  // and traced and shaded on the device as WavefrontRenderer does (rtx_radiance: fixed sampling,
+  // random numbers keyed by (seed, ids ? ids[i] : i, first_sample + k)); segments, if given, the
+  // segments traced per ray.  Not virtual: the reference's interface has no such call.
+  void RadianceBatch(const std::vector<core::Ray>& rays, std::vector<core::Vec3>& out, int spp, int max_depth,
+                     uint64_t seed, const std::vector<uint32_t>* ids = nullptr, int first_sample = 0,
+                     std::vector<uint32_t>* segments = nullptr) const {
+    out.resize(rays.size());
+    if (segments) segments->resize(rays.size());
+    if (rays.empty()) return;
+    if (ids && ids->size() != rays.size()) throw std::invalid_argument("RadianceBatch: one id per ray");
+    std::vector<rtx_ray> r(rays.size());
+    for (size_t i = 0; i < rays.size(); i++)
+      for (int k = 0; k < 3; k++) r[i].origin[k] = rays[i].origin()[k], r[i].direction[k] = rays[i].direction()[k];
+    rtx_radiance_params p{};
+    p.spp = spp, p.max_depth = max_depth, p.first_sample = first_sample, p.precision = precision_, p.seed = seed;
+    std::vector<double> rgb(3 * rays.size());
+    if (rtx_radiance(dev_, r.data(), ids ? ids->data() : nullptr, r.size(), &p, rgb.data(),
+                     segments ? segments->data() : nullptr) != RTX_OK)
+      throw std::runtime_error(std::string("rtx_radiance: ") + rtx_last_error());
+    for (size_t i = 0; i < rays.size(); i++) out[i] = core::Vec3(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]);
+  }
+
   rtx_scene* device_scene() const { return dev_; }
   const RtxScene& flat() const { return flat_; }
 
