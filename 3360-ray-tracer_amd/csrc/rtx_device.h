@@ -619,6 +619,7 @@ struct Counters {
 // summed over the rounds (wave-uniform: counted by lane 0 or the first active lane).
 struct CountersClk : Counters {
   uint64_t t_top, t_seg, t_walk, t_leaf;  // the current round's stamps (t_walk: set by the lanes that traced)
+  uint64_t t_sh;  // batched shading (k_persistent kShade > 1): the end of the round's shading stage
   uint64_t cyc_refill, cyc_walk, cyc_shade, cyc_leaf;
   uint32_t wshade, lshade;
 };
@@ -1405,6 +1406,28 @@ __device__ __forceinline__ const T* opaque(const T* p) {
   return p;
 }
 
+// The step of a path that ends on the sky: a miss, or a segment at the depth limit (whatever it
+// hit).  nd: the ray's unit direction.  shade_core's first branch and shade_terminal share it.
+__device__ __forceinline__ void shade_sky_end(V3 nd, ShadeOut& so) {
+  const double t = 0.5 * (nd.y + 1.0);  // sky() with ud = nd
+  so.f = (1.0 - t) * v3(1.0, 1.0, 1.0) + t * v3(0.5, 0.7, 1.0);
+  so.what = kShadeEmit;
+}
+// The radiance of a path terminated with kShadeEmit (shade_finish, shade_terminal)
+__device__ __forceinline__ V3 shade_emit(const ShadeOut& so, V3 thr) {
+  V3 L = v3(0, 0, 0);
+  return L + thr * so.f;
+}
+// The whole step of such a path, for a caller that knows the segment missed or is at the depth
+// limit before it shades (the persistent kernel, which ends those lanes right after the walk):
+// the operations shade_core and shade_finish perform for that lane, in their order.
+__device__ __forceinline__ V3 shade_terminal(V3 d, V3 thr) {
+  double lnd;
+  ShadeOut so;
+  shade_sky_end(normalize_l(d, lnd), so);
+  return shade_emit(so, thr);
+}
+
 // SET_ORIGIN = false: a continuing path's new origin (the hit point) is left for the caller
 // to set, so a caller that parked the hit point elsewhere keeps rec.p out of registers.
 // DEFER_F (texture-free builds): the BSDF value of a Lambertian / Metal hit is the material's
@@ -1419,9 +1442,7 @@ __device__ __forceinline__ void shade_core(const DScene& S, int max_depth, Path&
   double lnd;
   const V3 nd = normalize_l(p.d, lnd);  // wo = -nd (hit), sky(d) (miss)
   if (!hit || p.depth >= max_depth) {
-    const double t = 0.5 * (nd.y + 1.0);  // sky() with ud = nd
-    so.f = (1.0 - t) * v3(1.0, 1.0, 1.0) + t * v3(0.5, 0.7, 1.0);
-    so.what = kShadeEmit;
+    shade_sky_end(nd, so);
     return;
   }
   if (!LAMB) {  // Lambertian emits nothing (Material::Emitted default, material.h:50-54)
@@ -1545,7 +1566,7 @@ __device__ __forceinline__ bool shade_finish(const ShadeOut& so, V3& thr, int32_
                                              const rtx_material* m = nullptr) {
   L = v3(0, 0, 0);
   if (so.what == kShadeEmit) {
-    L = L + thr * so.f;
+    L = shade_emit(so, thr);
     return false;
   }
   if (so.what == kShadeDead) return false;

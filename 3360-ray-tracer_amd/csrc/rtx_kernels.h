@@ -27,6 +27,16 @@ constexpr int kSlotTargetLog2 = 29;  // persistent: up to 2^29 slots (pixel x sa
 constexpr int kRefillMin = 24;      // persistent lanes: refill once this many lanes of a wave are idle (ab_refill2_*)
 constexpr int kRefillMinPark = 12;  // the same for the PARK kernel (12 vs 16: C3 adaptive +0.5 %, fixed +-0; r9f / r9g)
 constexpr int kParkAt = 16;  // PARK kernel: park traversals once at most this many lanes still walk (ab_parkT_*)
+// PARK kernel: shade a wave's hits once this many of its lanes hold one (k_persistent kShade; 1:
+// every round shades what its walk found, 23.7 hits among 53 lanes on the bunny), for fixed spp
+// (MAP 0; C3: 16 +1.1 %, 24 +4.8 %, 32 +4.0 %, 40 +2.7 % over 1, profiles/r10/ab/ab_c3.txt); the
+// adaptive phases (MAP 1) shade every round, a threshold for them was not measured.
+// RTX_SHADE_MIN: the arms of that A/B (make variant V=s16 D=-DRTX_SHADE_MIN=16)
+#ifndef RTX_SHADE_MIN
+#define RTX_SHADE_MIN 24
+#endif
+constexpr int kShadeMinPark = RTX_SHADE_MIN;
+static_assert(kShadeMinPark >= 1 && kShadeMinPark <= 64, "lanes of a wave");
 // persistent: slots taken per atomic on a region's slot counter, by schedule (k_persistent
 // kChunk): the plain kernel 256 (ab_chunk_*; 512 C2 -0.4 %), the PARK kernel 512 (bunny C3
 // +0.7 %, profiles/r04/ab_chunk_map0_r6e_*.txt)
@@ -314,6 +324,11 @@ __global__ __launch_bounds__(kBlock, kTraceWaves) void k_wf_extend(RenderArgs A,
 // address (next_slot[130]), both written by k_adapt_expand.  MAP is a template parameter, not a
 // kernel argument: the fixed-spp kernels run at the SGPR limit, and any extra uniform state
 // there reshuffles their register allocation (a runtime switch cost the bunny's build 3.7 %, r3d).
+// A round of the loop: shade the wave's pending hits (PARK kernels with kShade > 1: once kShade
+// lanes hold one), refill the idle lanes, walk; a walk that ends on the sky ends its path at once,
+// one that found a hit to shade leaves the lane pending (kShade > 1) or is shaded in the same
+// round (kShade = 1: the plain kernel, the scatter API, the adaptive phases).  The threshold is a
+// compile-time constant for the same reason as MAP.
 template <int STACK, bool FAST, bool COUNT, bool SCATTER, int PARK, int TK = -1, bool LAMB = false,
           bool NOTEX = false, bool NODOF = false, int MAP = 0>
 __global__ __launch_bounds__(kBlock, kTraceWaves) void k_persistent(RenderArgs A, unsigned long long* next_slot) {
@@ -376,10 +391,88 @@ __global__ __launch_bounds__(kBlock, kTraceWaves) void k_persistent(RenderArgs A
   const bool park_ok = kPark && A.S.use_bvh && !A.S.froot_leaf;
   bool parked = false;
   TravState trs;
+  // Batched shading (kShade > 1).  A lane whose walk ended on a miss or at the depth limit ends its
+  // path right after the walk (shade_terminal: a normalize and the sky colour).  A lane whose walk
+  // found a hit below the depth limit becomes pending: it keeps the state a parked lane keeps
+  // (P.o, P.d, trs.best / closest / mat, pix, smp, P.depth, slot), sits out the walk rounds, and is
+  // shaded at a loop top together with the wave's other pending lanes once kShade of them wait, so
+  // the long f64 chain of the BSDF sampling issues for a fuller wave than the hits of one walk
+  // round make.  The flag is a sentinel in trs.node, which is dead once a walk has finished (a
+  // child word of the tree is a non-negative int32): no lane mask of its own, the kernel runs at
+  // the SGPR limit.  Each lane performs the same operations on the same operands in the same order
+  // as with kShade = 1, and a segment's RNG is keyed by (seed, pixel, sample, depth + 1), not by
+  // when it is shaded: the results are the same bit for bit.
+  constexpr int kRefill = kPark ? kRefillMinPark : kRefillMin;
+  constexpr int kShade = kPark && MAP == 0 ? kShadeMinPark : 1;
+  constexpr bool kBatch = kShade > 1;
+  constexpr uint32_t kPendNode = 0xFFFFFFFFu;
+  if (kBatch) trs.node = 0;
+  // the end of a path: its radiance record
+  auto end_path = [&](V3 L) {
+    store_radiance(A, slot, L);
+    if (COUNT && segbuf) segbuf[slot] = (uint16_t)min(pseg, 65535u);
+    has = false;
+  };
+  // the full shading of a traced segment (closest primitive `best` at distance tb, or a miss):
+  // false: the path ended with radiance L
+  auto shade_segment = [&](int64_t best, double tb, V3& L) -> bool {
+    bool cont;
+    Hit h;
+    rtx_material m;
+    if (best >= 0) finish_hit_at<false>(A.S, best, tb, P.o, P.d, h);
+    if (kHitpLds && best >= 0) hitp_lds[0] = h.p.x, hitp_lds[kBlock] = h.p.y, hitp_lds[2 * kBlock] = h.p.z;
+    if (best >= 0) m = A.S.mats[h.mat];
+    if (SCATTER) P.thr = v3(thr_lds[0], thr_lds[kBlock], thr_lds[2 * kBlock]);
+    // stream of this segment: depth + 1 (GetPixel: depth counts down from max_depth)
+    Rng g = make_rng(A.seed, pix, smp, SCATTER ? (uint32_t)(A.max_depth - P.depth) + 1u : (uint32_t)P.depth + 1u);
+    if (SCATTER) {
+      // GetPixel(r, depth) iteratively (camera.h:148-174); P.thr holds the product of the
+      // attenuations, P.depth the remaining depth.  Emitters never scatter, so the
+      // recursion's emitted terms reduce to the terminal one.
+      if (best < 0) {
+        L = P.thr * sky(P.d);
+        cont = false;
+      } else {
+        V3 att, sd;
+        if (mat_scatter(A.S, m, P.d, h, att, sd, g)) {
+          P.thr = P.thr * att;
+          P.o = h.p, P.d = sd;
+          P.depth--;
+          cont = true;
+        } else {
+          L = P.thr * mat_emitted(A.S, m, h);
+          cont = false;
+        }
+      }
+      if (cont) thr_lds[0] = P.thr.x, thr_lds[kBlock] = P.thr.y, thr_lds[2 * kBlock] = P.thr.z;
+    } else {
+      // the throughput is read from LDS only after the shading core: none of its registers
+      // are live across the walk or the BSDF sampling; the material's fields are read where
+      // shading uses them (a reference into the table, not a copy loaded up front and held
+      // across the sampling)
+      ShadeOut so;
+      const rtx_material& mr = *opaque(A.S.mats + (best >= 0 ? h.mat : 0));
+      shade_core<LAMB, NOTEX, !kHitpLds>(A.S, A.max_depth, P, h, best >= 0, g, mr, so);
+      V3 thr = v3(thr_lds[0], thr_lds[kBlock], thr_lds[2 * kBlock]);
+      cont = shade_finish(so, thr, P.depth, g, L, best >= 0 ? A.S.mats + h.mat : A.S.mats);
+      if (cont) thr_lds[0] = thr.x, thr_lds[kBlock] = thr.y, thr_lds[2 * kBlock] = thr.z;
+      if (kHitpLds && cont) P.o = v3(hitp_lds[0], hitp_lds[kBlock], hitp_lds[2 * kBlock]);
+    }
+    return cont;
+  };
   while (true) {
     // counting builds: region stamps (s_memtime, wave-uniform); t_walk is set by the lanes that
     // traced this round and read here, at the next loop top, where the wave has reconverged
-    if constexpr (COUNT) {
+    if constexpr (COUNT && kBatch) {
+      // batched shading: a round is shading (pending lanes) .. refill .. walk, the cheap
+      // terminals on the walk's side; every stamp is taken where the wave is converged
+      const uint64_t now = __builtin_amdgcn_s_memtime();
+      if (lane_id() == 0) {
+        if (c.t_seg) c.cyc_refill += c.t_seg - c.t_sh, c.cyc_walk += now - c.t_seg;
+        else if (c.t_top) c.cyc_refill += now - c.t_sh;  // (a round with nothing to trace)
+      }
+      c.t_top = now, c.t_sh = now, c.t_seg = 0;
+    } else if constexpr (COUNT) {
       const uint64_t now = __builtin_amdgcn_s_memtime();
       const unsigned long long tw = __ballot(c.t_walk != 0);
       if (c.t_seg && tw) {  // the previous round traced: refill .. walk .. shading
@@ -390,14 +483,43 @@ __global__ __launch_bounds__(kBlock, kTraceWaves) void k_persistent(RenderArgs A
       }
       c.t_top = now, c.t_seg = 0, c.t_walk = 0;
     }
+    // ---- batched shading: the pending lanes, once kShade of them wait.  Every round must shade,
+    // refill or walk, or the wave would spin (the end of a launch, a frame of fewer than kShade
+    // slots): fewer pending lanes are shaded at once when the wave can draw no more slots
+    // (exhausted), and when no lane is left walking and the idle lanes are too few for the refill
+    // below to run.  Otherwise this round walks its unfinished (parked) lanes, each such round
+    // finishing at least one of them, or, with none left, refills (or finds the slots used up).
+    if constexpr (kBatch) {
+      const bool pend = has && trs.node == kPendNode;
+      const unsigned long long pm = __ballot(pend);
+      if (pm != 0) {
+        const int np = __popcll(pm), ni = __popcll(__ballot(!has));
+        if (np >= kShade || exhausted || (np + ni == 64 && ni < kRefill)) {
+          __builtin_amdgcn_s_setprio(0);  // (shading at the base priority, below)
+          if (pend) {
+            if constexpr (COUNT) {
+              if ((int)lane_id() == __ffsll((long long)pm) - 1) c.wshade++, c.lshade += (uint32_t)np;
+            }
+            V3 L;
+            const bool cont = shade_segment(trs.best, trs.closest, L);
+            trs.node = 0;
+            if (!cont) end_path(L);
+          }
+          if constexpr (COUNT) {
+            const uint64_t t = __builtin_amdgcn_s_memtime();
+            if (lane_id() == 0) c.cyc_shade += t - c.t_top;
+            c.t_sh = t;
+          }
+        }
+      }
+    }
     // ---- refill: ballot of idle lanes, leftover of the current chunk first.  Refilling
     // only once kRefillMin lanes are idle (or the wave is empty) amortises the
     // primary-generation code over several lanes.
     const unsigned long long idle = __ballot(!has);
     bool fresh = false;
     // (re-checked with the cheaper primary setup, FastDiv: PARK at 8 / 10, plain at 16 / 20 idle
-    // lanes within +-0.4 %, r10q)
-    constexpr int kRefill = kPark ? kRefillMinPark : kRefillMin;
+    // lanes within +-0.4 %, r10q; kRefill)
     if (kShared) {
       // block-shared chunks: the wave takes slots from its own chunk word (an LDS add), then from
       // a fresh chunk of the slot counters (installed in its word), and once the counters are
@@ -544,7 +666,7 @@ __global__ __launch_bounds__(kBlock, kTraceWaves) void k_persistent(RenderArgs A
       if (lane_id() == 0) c.wlive += live;
     }
     if constexpr (COUNT) c.t_seg = __builtin_amdgcn_s_memtime();
-    if (!has) continue;
+    if (!has || (kBatch && trs.node == kPendNode)) continue;  // idle, or waiting to be shaded
     // wave priority by phase: a wave walking (node visits, leaf tests) outranks one shading or
     // refilling, so the SIMD's issue slots go first to the walks, whose loads are the long
     // latencies (C3 +0.9 % over the load barriers alone; shading above walking, or leaf rounds
@@ -564,8 +686,12 @@ __global__ __launch_bounds__(kBlock, kTraceWaves) void k_persistent(RenderArgs A
         const int active = __popcll(__ballot(1));  // lanes tracing this round
         if (!parked) {
           trav_init(trs, kInf);
-          // the leaf-step walk's Lambertian texture-free kind-specialised build spills more with
-          // the plain-sphere test (scratch 52 -> 84 B per lane, profiles/r07): it keeps the generic one
+          // the leaf-step walk's Lambertian texture-free kind-specialised build keeps the generic
+          // test: round 7 kept it for the build's frame size (52 -> 84 B with the plain-sphere test)
+          // at +0.1 %.  Since round 10 the build's frame is 84 B with either test (117 / 115 VGPRs),
+          // and no instruction of it touches scratch: the frame of these Lambertian texture-free
+          // builds is slots of SGPR spills that live in VGPR lanes (profiles/r10/README.md).  The
+          // plain-sphere test was not timed again for this build.
           constexpr bool kGlobalSph = !(PARK == 1 && TK >= 0 && LAMB && NOTEX && MAP == 0);
           trav_globals<COUNT, kGlobalSph>(A.S, P.o, P.d, tmin, c, trs);
         }
@@ -590,57 +716,25 @@ __global__ __launch_bounds__(kBlock, kTraceWaves) void k_persistent(RenderArgs A
       if constexpr (COUNT) {
         pseg++;
         if (!kPark || !park_ok) c.t_walk = __builtin_amdgcn_s_memtime();
-        const unsigned long long sh = __ballot(1);
-        if ((int)lane_id() == __ffsll((long long)sh) - 1) c.wshade++, c.lshade += (uint32_t)__popcll(sh);
+        if constexpr (!kBatch) {
+          const unsigned long long sh = __ballot(1);
+          if ((int)lane_id() == __ffsll((long long)sh) - 1) c.wshade++, c.lshade += (uint32_t)__popcll(sh);
+        }
       }
       __builtin_amdgcn_s_setprio(0);  // shading (and the refill after it) at the base priority
-      Hit h;
-      rtx_material m;
-      if (best >= 0) finish_hit_at<false>(A.S, best, tb, P.o, P.d, h);
-      if (kHitpLds && best >= 0) hitp_lds[0] = h.p.x, hitp_lds[kBlock] = h.p.y, hitp_lds[2 * kBlock] = h.p.z;
-      if (best >= 0) m = A.S.mats[h.mat];
-      if (SCATTER) P.thr = v3(thr_lds[0], thr_lds[kBlock], thr_lds[2 * kBlock]);
-      // stream of this segment: depth + 1 (GetPixel: depth counts down from max_depth)
-      Rng g = make_rng(A.seed, pix, smp, SCATTER ? (uint32_t)(A.max_depth - P.depth) + 1u : (uint32_t)P.depth + 1u);
-      if (SCATTER) {
-        // GetPixel(r, depth) iteratively (camera.h:148-174); P.thr holds the product of the
-        // attenuations, P.depth the remaining depth.  Emitters never scatter, so the
-        // recursion's emitted terms reduce to the terminal one.
-        if (best < 0) {
-          L = P.thr * sky(P.d);
+      if constexpr (kBatch) {
+        if (best < 0 || P.depth >= A.max_depth) {  // ends on the sky: at once
+          L = shade_terminal(P.d, v3(thr_lds[0], thr_lds[kBlock], thr_lds[2 * kBlock]));
           cont = false;
-        } else {
-          V3 att, sd;
-          if (mat_scatter(A.S, m, P.d, h, att, sd, g)) {
-            P.thr = P.thr * att;
-            P.o = h.p, P.d = sd;
-            P.depth--;
-            cont = true;
-          } else {
-            L = P.thr * mat_emitted(A.S, m, h);
-            cont = false;
-          }
+        } else {  // a hit to shade: pending, until the wave shades its pending lanes (loop top)
+          trs.best = (int32_t)best, trs.closest = tb, trs.node = kPendNode;
+          cont = true;
         }
-        if (cont) thr_lds[0] = P.thr.x, thr_lds[kBlock] = P.thr.y, thr_lds[2 * kBlock] = P.thr.z;
       } else {
-        // the throughput is read from LDS only after the shading core: none of its registers
-        // are live across the walk or the BSDF sampling; the material's fields are read where
-        // shading uses them (a reference into the table, not a copy loaded up front and held
-        // across the sampling)
-        ShadeOut so;
-        const rtx_material& mr = *opaque(A.S.mats + (best >= 0 ? h.mat : 0));
-        shade_core<LAMB, NOTEX, !kHitpLds>(A.S, A.max_depth, P, h, best >= 0, g, mr, so);
-        V3 thr = v3(thr_lds[0], thr_lds[kBlock], thr_lds[2 * kBlock]);
-        cont = shade_finish(so, thr, P.depth, g, L, best >= 0 ? A.S.mats + h.mat : A.S.mats);
-        if (cont) thr_lds[0] = thr.x, thr_lds[kBlock] = thr.y, thr_lds[2 * kBlock] = thr.z;
-        if (kHitpLds && cont) P.o = v3(hitp_lds[0], hitp_lds[kBlock], hitp_lds[2 * kBlock]);
+        cont = shade_segment(best, tb, L);
       }
     }
-    if (!cont) {
-      store_radiance(A, slot, L);
-      if (COUNT && segbuf) segbuf[slot] = (uint16_t)min(pseg, 65535u);
-      has = false;
-    }
+    if (!cont) end_path(L);
   }
   flush_counters(A, c, segs, prims, COUNT);
   if constexpr (COUNT) flush_clock(A, c);
