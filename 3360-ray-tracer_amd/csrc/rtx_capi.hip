@@ -26,6 +26,7 @@
 #include "rtx_occlusion.h"
 #include "rtx_p3.h"
 #include "rtx_radiance.h"
+#include "rtx_irradiance.h"
 #include "rtx_scan.h"
 
 using namespace rtxd;
@@ -799,7 +800,15 @@ int launch_radiance(rtx_scene* sc, const RadianceChunk& A, hipStream_t s) {
   HIPC(hipGetLastError());
   return RTX_OK;
 }
-// the checks rtx_radiance and rtx_radiance_device share, in the documented order
+// the same launch of k_irradiance (rtx_irradiance.h): A.rays are surfels
+template <int STACK, bool FAST>
+int launch_irradiance(rtx_scene* sc, const RadianceChunk& A, hipStream_t s) {
+  hipLaunchKernelGGL((k_irradiance<STACK, FAST>), dim3((A.slots + kBlock - 1) / kBlock), dim3(kBlock),
+                     stack_lds_bytes(STACK), s, sc->S, A);
+  HIPC(hipGetLastError());
+  return RTX_OK;
+}
+// the checks rtx_radiance*, rtx_irradiance* and rtx_internal_irradiance_rays share, in the documented order
 int radiance_check(const rtx_scene* sc, const rtx_radiance_params* prm, const void* rays, const void* out) {
   if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
   if (!prm) return fail(RTX_ERR_INVALID, "NULL argument");
@@ -815,9 +824,10 @@ int radiance_check(const rtx_scene* sc, const rtx_radiance_params* prm, const vo
 // n > 0 rays on device buffers, in chunks of at most `cap` slots (ray x sample): whole rays per
 // chunk, or, when one ray's samples exceed the cap, one ray at a time in runs of `cap` samples
 // whose partial sum k_radiance_sum carries.  id_base: the pixel key of d_rays[0] when d_ids is
-// null (the host entry point's batches).
+// null (the host entry point's batches).  irr: d_rays are surfels and the slots are k_irradiance's
+// (rtx_irradiance*); the chunking, the scratch and the sum are the same.
 int radiance_on(rtx_scene* sc, const rtx_ray* d_rays, const uint32_t* d_ids, uint64_t id_base, int64_t n,
-                const rtx_radiance_params* prm, double* d_out, uint32_t* d_segs, hipStream_t s) {
+                const rtx_radiance_params* prm, double* d_out, uint32_t* d_segs, hipStream_t s, bool irr = false) {
   const int64_t tuned = g_radiance_chunk.load();
   const int64_t cap = std::min<int64_t>(tuned > 0 ? tuned : kRadianceSlots, kRadianceSlotsMax);
   const int64_t spp = prm->spp;
@@ -842,7 +852,10 @@ int radiance_on(rtx_scene* sc, const rtx_ray* d_rays, const uint32_t* d_ids, uin
       A.slots = (uint32_t)(nr * K), A.K = (uint32_t)K;
       A.s0 = (int32_t)(prm->first_sample + k0), A.max_depth = prm->max_depth, A.seed = prm->seed;
       A.L = sc->rad_L.as<double>(), A.segs = sc->rad_segs.as<uint32_t>();
-      if (fast) rc = st == 32 ? launch_radiance<32, true>(sc, A, s) : launch_radiance<64, true>(sc, A, s);
+      if (irr) {
+        if (fast) rc = st == 32 ? launch_irradiance<32, true>(sc, A, s) : launch_irradiance<64, true>(sc, A, s);
+        else rc = st == 32 ? launch_irradiance<32, false>(sc, A, s) : launch_irradiance<64, false>(sc, A, s);
+      } else if (fast) rc = st == 32 ? launch_radiance<32, true>(sc, A, s) : launch_radiance<64, true>(sc, A, s);
       else rc = st == 32 ? launch_radiance<32, false>(sc, A, s) : launch_radiance<64, false>(sc, A, s);
       if (rc) return rc;
       hipLaunchKernelGGL(k_radiance_sum, dim3((unsigned)((nr + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
@@ -1601,8 +1614,9 @@ int rtx_radiance_device(rtx_scene* sc, const rtx_ray* d_rays, const uint32_t* d_
 // The host entry point works in batches of kRadianceHostRays rays: the caller's rays and ids are
 // copied into pinned memory, traced, and the results copied back out of it.
 constexpr size_t kRadianceHostRays = (size_t)1 << 20;
-int rtx_radiance(rtx_scene* sc, const rtx_ray* rays, const uint32_t* ids, size_t n, const rtx_radiance_params* prm,
-                 double* out_rgb, uint32_t* out_segments) {
+// (shared with rtx_irradiance, irr: the rays are surfels)
+static int radiance_host(rtx_scene* sc, const rtx_ray* rays, const uint32_t* ids, size_t n,
+                         const rtx_radiance_params* prm, double* out_rgb, uint32_t* out_segments, bool irr) {
   int rc;
   if ((rc = radiance_check(sc, prm, rays, out_rgb))) return rc;
   if (n == 0) return RTX_OK;
@@ -1626,7 +1640,7 @@ int rtx_radiance(rtx_scene* sc, const rtx_ray* rays, const uint32_t* ids, size_t
       HIPC(hipMemcpyAsync(sc->rad_ids.p, pin + off_ids, nb * sizeof(uint32_t), hipMemcpyHostToDevice, sc->stream));
     }
     if ((rc = radiance_on(sc, sc->rays.as<rtx_ray>(), ids ? sc->rad_ids.as<uint32_t>() : nullptr, (uint64_t)b0,
-                          (int64_t)nb, prm, sc->rad_out.as<double>(), sc->rad_oseg.as<uint32_t>(), sc->stream)))
+                          (int64_t)nb, prm, sc->rad_out.as<double>(), sc->rad_oseg.as<uint32_t>(), sc->stream, irr)))
       return rc;
     HIPC(hipMemcpyAsync(pin + off_rgb, sc->rad_out.p, nb * 3 * sizeof(double), hipMemcpyDeviceToHost, sc->stream));
     if (out_segments)
@@ -1635,6 +1649,55 @@ int rtx_radiance(rtx_scene* sc, const rtx_ray* rays, const uint32_t* ids, size_t
     std::memcpy(out_rgb + 3 * b0, pin + off_rgb, nb * 3 * sizeof(double));
     if (out_segments) std::memcpy(out_segments + b0, pin + off_seg, nb * sizeof(uint32_t));
   }
+  return RTX_OK;
+}
+int rtx_radiance(rtx_scene* sc, const rtx_ray* rays, const uint32_t* ids, size_t n, const rtx_radiance_params* prm,
+                 double* out_rgb, uint32_t* out_segments) {
+  return radiance_host(sc, rays, ids, n, prm, out_rgb, out_segments, false);
+}
+
+// ---- irradiance queries (rtx_irradiance.h): rtx_radiance's checks, chunks and staging ----
+int rtx_irradiance_device(rtx_scene* sc, const rtx_ray* d_surfels, const uint32_t* d_ids, size_t n,
+                          const rtx_radiance_params* prm, double* d_out_rgb, uint32_t* d_out_segments, void* stream) {
+  int rc;
+  if ((rc = radiance_check(sc, prm, d_surfels, d_out_rgb))) return rc;
+  if (n == 0) return RTX_OK;
+  HIPC(hipSetDevice(sc->device));
+  return radiance_on(sc, d_surfels, d_ids, 0, (int64_t)n, prm, d_out_rgb, d_out_segments,
+                     stream ? (hipStream_t)stream : sc->stream, true);
+}
+
+int rtx_irradiance(rtx_scene* sc, const rtx_ray* surfels, const uint32_t* ids, size_t n,
+                   const rtx_radiance_params* prm, double* out_rgb, uint32_t* out_segments) {
+  return radiance_host(sc, surfels, ids, n, prm, out_rgb, out_segments, true);
+}
+
+// Test hook (not in rtx.h): the depth-0 segments rtx_irradiance traces for the same arguments
+// (seed, first_sample and spp of prm are read; the rest is checked as there), n x spp x 6
+// doubles (origin, direction), surfel major, made by the device function k_irradiance calls
+// (irradiance_ray, rtx_irradiance.h); all zero for a surfel with a degenerate normal.  Host
+// buffers.
+extern "C" int rtx_internal_irradiance_rays(rtx_scene* sc, const rtx_ray* surfels, const uint32_t* ids, size_t n,
+                                            const rtx_radiance_params* prm, double* out) {
+  int rc;
+  if ((rc = radiance_check(sc, prm, surfels, out))) return rc;
+  if (n == 0) return RTX_OK;
+  if (n > (size_t)kRadianceSlotsMax || (int64_t)n * prm->spp > kRadianceSlotsMax)
+    return fail(RTX_ERR_INVALID, "irradiance rays: too many rays for one call");
+  HIPC(hipSetDevice(sc->device));
+  const uint32_t nslots = (uint32_t)(n * (size_t)prm->spp);
+  const size_t bytes = (size_t)nslots * 6 * sizeof(double);
+  if ((rc = sc->rays.reserve(n * sizeof(rtx_ray)))) return rc;
+  if ((rc = sc->rad_L.reserve(bytes))) return rc;
+  if (ids && (rc = sc->rad_ids.reserve(n * sizeof(uint32_t)))) return rc;
+  HIPC(hipMemcpyAsync(sc->rays.p, surfels, n * sizeof(rtx_ray), hipMemcpyHostToDevice, sc->stream));
+  if (ids) HIPC(hipMemcpyAsync(sc->rad_ids.p, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, sc->stream));
+  hipLaunchKernelGGL(k_irradiance_rays, dim3((nslots + kBlock - 1) / kBlock), dim3(kBlock), 0, sc->stream,
+                     sc->rays.as<rtx_ray>(), ids ? sc->rad_ids.as<uint32_t>() : nullptr, nslots, (uint32_t)prm->spp,
+                     prm->seed, prm->first_sample, sc->rad_L.as<double>());
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(out, sc->rad_L.p, bytes, hipMemcpyDeviceToHost, sc->stream));
+  HIPC(hipStreamSynchronize(sc->stream));
   return RTX_OK;
 }
 

@@ -206,9 +206,10 @@ __device__ __forceinline__ AoHit ao_first_hit(const DScene& S, const rtx_camera&
 // (RandomCosineDirection over an ONB about n, the operations of the Lambertian chain in
 // shade_core: r1, r2 drawn in that order, phi = 2 pi r1, (sqrt(r2) cos phi, sqrt(r2) sin phi,
 // sqrt(1 - r2)) in the basis u = v x w, v = normalize(w x a), w = normalize(n)), from stream
-// kRngStreamAo of (seed, pix, sample).  Both k_ao and k_ao_rays call this function.
-__device__ __forceinline__ V3 ao_direction(uint64_t seed, uint32_t pix, uint32_t sample, V3 n) {
-  Rng g = make_rng(seed, pix, sample, kRngStreamAo);
+// `stream` of (seed, pix, sample): kRngStreamAo for the AO pass (ao_direction: both k_ao and
+// k_ao_rays call it), kRngStreamIrr for the irradiance queries (rtx_irradiance.h).
+__device__ __forceinline__ V3 cosine_direction(uint64_t seed, uint32_t pix, uint32_t sample, uint32_t stream, V3 n) {
+  Rng g = make_rng(seed, pix, sample, stream);
   const double r1 = g.next(), r2 = g.next();
   const V3 w = normalize(n);
   const V3 a = (fabs(w.x) > 0.9) ? v3(0, 1, 0) : v3(1, 0, 0);
@@ -220,6 +221,9 @@ __device__ __forceinline__ V3 ao_direction(uint64_t seed, uint32_t pix, uint32_t
   const double s = sqrt(r2);
   const double x = s * cph, y = s * sph, z = sqrt(1.0 - r2);
   return normalize(x * u + y * v + z * w);
+}
+__device__ __forceinline__ V3 ao_direction(uint64_t seed, uint32_t pix, uint32_t sample, V3 n) {
+  return cosine_direction(seed, pix, sample, kRngStreamAo, n);
 }
 
 // One lane per pixel of the subset, in subset order: the first hit, then `samples` any-hit rays

@@ -48,6 +48,16 @@ class GpuRayIntegrator : public RayIntegrator {
   // reference's RayIntegrator interface.
   void OccludedBatch(const std::vector<core::Ray>& rays, std::vector<uint8_t>& out,
                      double tmax = core::kInfinity) const;
+  // Irradiance query: out[i] = the cosine-weighted mean radiance arriving at points[i] over the
+  // hemisphere about normals[i] (any positive finite length), from `samples` paths per point
+  // traced and shaded on the device (rtx_irradiance: directions keyed by (seed, ids ? ids[i] : i,
+  // first_sample + k)); pi times it is the radiometric irradiance.  A zero or non-finite normal
+  // gives 0 0 0.  segments, if given: the segments traced per point.  Not part of the reference's
+  // RayIntegrator interface.
+  void IrradianceBatch(const std::vector<core::Point3>& points, const std::vector<core::Vec3>& normals,
+                       std::vector<core::Vec3>& out, int samples, int max_depth, uint64_t seed,
+                       const std::vector<uint32_t>* ids = nullptr, int first_sample = 0,
+                       std::vector<uint32_t>* segments = nullptr) const;
   rtx_scene* device_scene() const { return dev_; }
   // Replace primitives [first, first + prims.size()) of the device copy, in its own order (leaf
   // order for a BVH world), and refit its trees in place (rtx_scene_update_prims): kinds stay,

@@ -66,6 +66,28 @@ void GpuRayIntegrator::OccludedBatch(const std::vector<core::Ray>& rays, std::ve
   check(rtx_occluded(dev_, r.data(), r.size(), out.data(), RTX_SEAM_TMIN, tmax, precision_), "rtx_occluded");
 }
 
+// The cosine-weighted mean radiance arriving at each point about its normal (rtx_irradiance).
+void GpuRayIntegrator::IrradianceBatch(const std::vector<core::Point3>& points, const std::vector<core::Vec3>& normals,
+                                       std::vector<core::Vec3>& out, int samples, int max_depth, uint64_t seed,
+                                       const std::vector<uint32_t>* ids, int first_sample,
+                                       std::vector<uint32_t>* segments) const {
+  if (normals.size() != points.size()) throw std::invalid_argument("IrradianceBatch: one normal per point");
+  out.resize(points.size());
+  if (segments) segments->resize(points.size());
+  if (points.empty()) return;
+  if (ids && ids->size() != points.size()) throw std::invalid_argument("IrradianceBatch: one id per point");
+  std::vector<rtx_ray> s(points.size());
+  for (size_t i = 0; i < points.size(); i++)
+    for (int k = 0; k < 3; k++) s[i].origin[k] = points[i][k], s[i].direction[k] = normals[i][k];
+  rtx_radiance_params p{};
+  p.spp = samples, p.max_depth = max_depth, p.first_sample = first_sample, p.precision = precision_, p.seed = seed;
+  std::vector<double> rgb(3 * points.size());
+  check(rtx_irradiance(dev_, s.data(), ids ? ids->data() : nullptr, s.size(), &p, rgb.data(),
+                       segments ? segments->data() : nullptr),
+        "rtx_irradiance");
+  for (size_t i = 0; i < points.size(); i++) out[i] = core::Vec3(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]);
+}
+
 }  // namespace rt::integrator
 
 namespace rt::renderer {

@@ -143,7 +143,8 @@ EXPORTS = ["rtx_abi_version", "rtx_last_error", "rtx_device_count", "rtx_scene_c
            "rtx_film_blob_check", "rtx_denoise_params_default", "rtx_aov", "rtx_aov_device", "rtx_denoise",
            "rtx_denoise_device", "rtx_film_denoise", "rtx_film_denoise_p3", "rtx_scene_update_prims",
            "rtx_scene_update_geometry_device", "rtx_scene_epoch", "rtx_bvh_refit_host", "rtx_film_reset",
-           "rtx_occluded", "rtx_occluded_device", "rtx_ao", "rtx_ao_device", "rtx_radiance", "rtx_radiance_device"]
+           "rtx_occluded", "rtx_occluded_device", "rtx_ao", "rtx_ao_device", "rtx_radiance", "rtx_radiance_device",
+           "rtx_irradiance", "rtx_irradiance_device"]
 
 _lib = None
 
@@ -217,6 +218,8 @@ def lib():
             "rtx_ao_device": ([vp, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(AoParams), vp, vp], C.c_int),
             "rtx_radiance": ([vp, vp, vp, sz, C.POINTER(RadianceParams), vp, vp], C.c_int),
             "rtx_radiance_device": ([vp, vp, vp, sz, C.POINTER(RadianceParams), vp, vp, vp], C.c_int),
+            "rtx_irradiance": ([vp, vp, vp, sz, C.POINTER(RadianceParams), vp, vp], C.c_int),
+            "rtx_irradiance_device": ([vp, vp, vp, sz, C.POINTER(RadianceParams), vp, vp, vp], C.c_int),
         }
         for name, (args, res) in sig.items():
             f = getattr(L, name)
@@ -435,6 +438,41 @@ class DeviceScene:
         _check(lib().rtx_radiance_device(self.h, C.c_void_p(d_rays), C.c_void_p(d_ids) if d_ids else None, n,
                                          C.byref(p), C.c_void_p(d_out), C.c_void_p(d_segments) if d_segments else None,
                                          C.c_void_p(stream) if stream else None), "rtx_radiance_device")
+
+    def irradiance(self, points, normals, samples, max_depth, seed=1234, ids=None, first_sample=0, precision="parity",
+                   segments=False):
+        """Irradiance query (rtx_irradiance): (n, 3), the cosine-weighted mean radiance arriving at
+        each point over the hemisphere about its normal (any positive finite length), from
+        `samples` paths per point traced and shaded as radiance() does; pi times it is the
+        radiometric irradiance.  Sample k of point i draws from (seed, pixel = ids[i] or i,
+        sample = first_sample + k) and equals radiance() of its ray (irradiance_rays) with that id,
+        spp = 1 and first_sample + k.  A zero or non-finite normal gives 0 0 0 and 0 segments.
+        segments=True: also the (n,) uint32 segments traced per point."""
+        surfels = _surfels(points, normals)
+        n = len(surfels)
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+            if len(ids) != n:
+                raise ValueError("irradiance: one id per point")
+        out = np.zeros((n, 3))
+        segs = np.zeros(n, np.uint32) if segments else None
+        p = self._radiance_params(samples, max_depth, seed, first_sample, precision)
+        _check(lib().rtx_irradiance(self.h, surfels.ctypes.data_as(C.c_void_p),
+                                    None if ids is None else ids.ctypes.data_as(C.c_void_p), n, C.byref(p),
+                                    out.ctypes.data_as(C.c_void_p),
+                                    None if segs is None else segs.ctypes.data_as(C.c_void_p)), "rtx_irradiance")
+        return (out, segs) if segments else out
+
+    def irradiance_device(self, d_surfels, n, d_out, samples, max_depth, seed=1234, first_sample=0, precision="parity",
+                          d_ids=0, d_segments=0, stream=0):
+        """The same on device buffers (rtx_irradiance_device): d_surfels names n x 6 doubles (point,
+        normal), d_out n x 3 doubles, d_ids n uint32 (0: the point's index), d_segments n uint32
+        (0: none), e.g. torch tensors' data_ptr().  Asynchronous."""
+        p = self._radiance_params(samples, max_depth, seed, first_sample, precision)
+        _check(lib().rtx_irradiance_device(self.h, C.c_void_p(d_surfels), C.c_void_p(d_ids) if d_ids else None, n,
+                                           C.byref(p), C.c_void_p(d_out),
+                                           C.c_void_p(d_segments) if d_segments else None,
+                                           C.c_void_p(stream) if stream else None), "rtx_irradiance_device")
 
     def _ao_args(self, cam, samples, radius, seed, tile, stripes, precision):
         p = RenderParams()
@@ -690,6 +728,35 @@ def camera_rays(scene, cam, spp, seed=1234, first_sample=0, tile=None, stripes=N
     out = np.zeros((n, spp, 6))
     _check(f(scene.h, C.byref(cam), C.byref(p), first_sample, spp, out.ctypes.data_as(C.c_void_p)),
            "rtx_internal_camera_rays")
+    return out
+
+
+def _surfels(points, normals):
+    """(n, 6) doubles: point, normal (the rtx_ray layout of rtx_irradiance's surfels)."""
+    points = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    normals = np.asarray(normals, dtype=np.float64).reshape(-1, 3)
+    if len(points) != len(normals):
+        raise ValueError("irradiance: one normal per point")
+    return np.ascontiguousarray(np.concatenate([points, normals], axis=1))
+
+
+def irradiance_rays(scene, points, normals, samples, seed, ids=None, first_sample=0):
+    """Test hook (rtx_internal_irradiance_rays, not in rtx.h): the depth-0 segments
+    DeviceScene.irradiance traces for the same arguments, (n, samples, 6), from the device
+    function the irradiance kernel calls; all zero for a point with a degenerate normal."""
+    surfels = _surfels(points, normals)
+    n = len(surfels)
+    if ids is not None:
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        if len(ids) != n:
+            raise ValueError("irradiance: one id per point")
+    f = lib().rtx_internal_irradiance_rays
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RadianceParams), C.c_void_p]
+    f.restype = C.c_int
+    p = DeviceScene._radiance_params(samples, 0, seed, first_sample, "parity")
+    out = np.zeros((n, samples, 6))
+    _check(f(scene.h, surfels.ctypes.data_as(C.c_void_p), None if ids is None else ids.ctypes.data_as(C.c_void_p), n,
+             C.byref(p), out.ctypes.data_as(C.c_void_p)), "rtx_internal_irradiance_rays")
     return out
 
 

@@ -4,7 +4,7 @@
 //             [--mode wavefront|persistent|megakernel] [--precision parity|fast]
 //             [--mk-adaptive MIN:THRESHOLD] [--gpus N]
 //             [--chunks N] [--preview PREFIX] [--checkpoint FILE] [--resume FILE] [--denoise]
-//             [--ao N[,RADIUS]] > out.ppm
+//             [--ao N[,RADIUS]] [--irradiance N[,DEPTH]] > out.ppm
 // --gpus N renders one frame over N GPUs (interleaved row stripes, one host thread per GPU,
 // one gathered framebuffer and P3 output; identical pixels for every N); --devices 0,2,3
 // names the devices (a device may repeat: several streams on one GPU).
@@ -20,6 +20,11 @@
 // any-hit rays of length RADIUS from each pixel's first hit; default RADIUS a quarter of the
 // scene's bounding-box diagonal) as a grey P3 PPM, AO replicated into R, G and B, through the
 // device encoder; --seed and --precision apply.  Without the flag no output changes.
+// --irradiance N[,DEPTH] writes the irradiance pass instead of a render (rtx_irradiance: at each
+// pixel's first hit, the cosine-weighted mean of the radiance of N paths of at most DEPTH bounces
+// over the hemisphere about the hit's normal, keyed by the global pixel; default DEPTH the
+// preset's max depth, or --depth; black where the pixel's ray misses) as a P3 PPM through the
+// device encoder; --seed and --precision apply.
 // --mk-adaptive selects the AdaptiveSampler (sampler.h:44-82) for --mode megakernel,
 // with max_samples = the preset's (or --spp) samples.
 // Defaults follow main.cc: preset "default" (fallback when unknown), the Cornell box
@@ -47,6 +52,8 @@ int main(int argc, char** argv) {
   bool fixed = false, denoise = false;
   std::vector<int> devices;
   int mk_min = -1, gpus = 1, chunks = 0, ao_samples = 0;
+  int irr_samples = 0, irr_depth = -1;  // --irradiance (depth -1: the preset's)
+  bool irr = false;
   double ao_radius = 0.0;  // 0: a quarter of the scene's bounding-box diagonal
   std::string preview, checkpoint, resume;
   float mk_thr = 0.0f;
@@ -80,6 +87,17 @@ int main(int argc, char** argv) {
       if (c != std::string::npos) ao_radius = std::strtod(v.substr(c + 1).c_str(), nullptr);
       if (ao_samples < 1 || ao_samples > 1024 || (c != std::string::npos && !(ao_radius > 0))) {
         std::cerr << "--ao expects N[,RADIUS] with N in 1..1024 and RADIUS > 0\n";
+        return 2;
+      }
+    }
+    else if (a == "--irradiance") {
+      const std::string v = next();
+      const size_t c = v.find(',');
+      irr = true;
+      irr_samples = std::atoi(v.substr(0, c).c_str());
+      if (c != std::string::npos) irr_depth = std::atoi(v.substr(c + 1).c_str());
+      if (irr_samples < 1 || (c != std::string::npos && irr_depth < 0)) {
+        std::cerr << "--irradiance expects N[,DEPTH] with N >= 1 and DEPTH >= 0\n";
         return 2;
       }
     }
@@ -161,6 +179,46 @@ int main(int argc, char** argv) {
         throw std::runtime_error(std::string("rtx_encode_p3: ") + rtx_last_error());
       std::cout.write(bytes.data(), (std::streamsize)len);
       std::clog << "AO: " << ao_samples << " samples, radius " << ao_radius << "\n";
+    } else if (irr) {
+      integrator::GpuRayIntegrator integ(world.get(), devices.empty() ? 0 : devices[0],
+                                         precision == "fast" ? RTX_PREC_FAST : RTX_PREC_PARITY);
+      const rtx_camera& dc = cam.device();
+      const int W = dc.image_width, H = dc.image_height;
+      const size_t npix = (size_t)W * (size_t)H;
+      // each pixel's centre ray (the ray of rtx_aov) and its first hit
+      std::vector<rtx_ray> rays(npix);
+      for (int y = 0; y < H; y++)
+        for (int x = 0; x < W; x++) {
+          rtx_ray& r = rays[(size_t)y * W + x];
+          for (int k = 0; k < 3; k++) {
+            r.origin[k] = dc.center[k];
+            r.direction[k] =
+                ((dc.pixel00[k] + ((double)x * dc.pixel_delta_u[k])) + ((double)y * dc.pixel_delta_v[k])) - dc.center[k];
+          }
+        }
+      std::vector<rtx_hit> hits(npix);
+      if (rtx_intersect(integ.device_scene(), rays.data(), npix, hits.data(), RTX_SEAM_TMIN, core::kInfinity,
+                        integ.precision()) != RTX_OK)
+        throw std::runtime_error(std::string("rtx_intersect: ") + rtx_last_error());
+      // surfels: the hit point and the record's normal; a zero normal (black) where the ray misses
+      std::vector<uint32_t> ids(npix);
+      for (size_t i = 0; i < npix; i++) {
+        ids[i] = (uint32_t)i;
+        for (int k = 0; k < 3; k++)
+          rays[i].origin[k] = hits[i].hit ? hits[i].p[k] : 0.0, rays[i].direction[k] = hits[i].hit ? hits[i].normal[k] : 0.0;
+      }
+      rtx_radiance_params rp{};
+      rp.spp = irr_samples, rp.max_depth = irr_depth >= 0 ? irr_depth : md, rp.first_sample = 0;
+      rp.precision = integ.precision(), rp.seed = seed;
+      std::vector<double> rgb(3 * npix);
+      if (rtx_irradiance(integ.device_scene(), rays.data(), ids.data(), npix, &rp, rgb.data(), nullptr) != RTX_OK)
+        throw std::runtime_error(std::string("rtx_irradiance: ") + rtx_last_error());
+      std::string bytes(rtx_p3_max_bytes(W, H), '\0');
+      size_t len = 0;
+      if (rtx_encode_p3(integ.device_scene(), rgb.data(), W, H, bytes.data(), bytes.size(), &len) != RTX_OK)
+        throw std::runtime_error(std::string("rtx_encode_p3: ") + rtx_last_error());
+      std::cout.write(bytes.data(), (std::streamsize)len);
+      std::clog << "irradiance: " << irr_samples << " samples, depth " << rp.max_depth << "\n";
     } else if (mode == "megakernel") {
       integrator::DefaultSampler fixed_sampler(ns);
       integrator::AdaptiveSampler adaptive_sampler(mk_min, ns, mk_thr);

@@ -518,6 +518,39 @@ int rtx_radiance_device(rtx_scene* scene, const rtx_ray* d_rays, const uint32_t*
                         const rtx_radiance_params* params, double* d_out_rgb, uint32_t* d_out_segments,
                         void* stream);
 
+/* ---- irradiance queries (DESIGN.md "Irradiance queries") -------------------------------------
+ * How much light arrives at these surface points?  The fused, ray-free consumer of the radiance
+ * query, for light probes, lightmap texels and per-vertex irradiance.  A surfel is an rtx_ray:
+ * `origin` is the point, `direction` the surface normal (any positive finite length: it is
+ * normalised on the device).  rtx_radiance_params is read as by rtx_radiance, spp being the
+ * samples per point.  For surfel i and sample k in [0, spp):
+ *   direction: a unit cosine-weighted vector about normalize(normal), made by the operations of
+ *     the AO pass's sample directions, from a Philox stream of its own keyed by (seed,
+ *     pixel = ids ? ids[i] : (uint32_t)i, sample = first_sample + k);
+ *   path: the ray (point, direction) is the depth-0 segment of a path with throughput 1, traced
+ *     and shaded exactly as rtx_radiance does (closest hit on (RTX_SEAM_TMIN, +inf) with the walk
+ *     of `precision`, segment d shading from stream d + 1 of the same key).
+ * So sample k of surfel i is, bit for bit, rtx_radiance of that one ray with the same id,
+ * spp = 1 and first_sample = first_sample + k.
+ * out_rgb: 3 doubles per surfel, the in-order sum of the spp radiances (from 0) times
+ * 1 / (double)(float)spp: the cosine-weighted mean incoming radiance, which is what a Lambertian
+ * texel multiplies by its albedo.  Irradiance in the radiometric sense is pi times this value.
+ * out_segments (may be NULL): segments traced for the surfel over all its samples.
+ * A surfel whose normal has a squared length that is not > 0 or not finite (zero or NaN normals,
+ * as in the padding texels of a lightmap) traces nothing: its output is 0 0 0 and its segment
+ * count 0.  This is decided on the device; the device variant never reads caller memory on the
+ * host.  Arguments are checked in rtx_radiance's order and with its messages (scene, params,
+ * buffers, spp, first_sample, max_depth, precision) before the scene or a device is touched;
+ * then n == 0 returns RTX_OK.  The live scene is read (after rtx_scene_update_* the new
+ * geometry); no film is involved.  One call at a time per scene. */
+/* Host buffers, staged through pinned memory in batches; returns when the outputs are written. */
+int rtx_irradiance(rtx_scene* scene, const rtx_ray* surfels, const uint32_t* ids, size_t n,
+                   const rtx_radiance_params* params, double* out_rgb, uint32_t* out_segments);
+/* Device buffers; asynchronous on stream (NULL = the scene's stream). */
+int rtx_irradiance_device(rtx_scene* scene, const rtx_ray* d_surfels, const uint32_t* d_ids, size_t n,
+                          const rtx_radiance_params* params, double* d_out_rgb, uint32_t* d_out_segments,
+                          void* stream);
+
 enum { RTX_DENOISE_DEMODULATE = 1 }; /* filter colour / max(albedo, 1e-3), multiply back at the end */
 typedef struct {
   int32_t iterations; /* 0..8; iteration k filters 5 x 5 taps at step 2^k; 0 copies the input */

@@ -90,6 +90,33 @@ class GpuRayIntegrator : public RayIntegrator {
     for (size_t i = 0; i < rays.size(); i++) out[i] = core::Vec3(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]);
   }
 
+  // Irradiance query: out[i] = the cosine-weighted mean radiance arriving at points[i] over the
+  // hemisphere about normals[i] (any positive finite length), from `samples` paths per point
+  // traced and shaded as RadianceBatch does (rtx_irradiance: directions keyed by (seed,
+  // ids ? ids[i] : i, first_sample + k)); pi times it is the radiometric irradiance, and a
+  // Lambertian texel multiplies it by its albedo.  A zero or non-finite normal gives 0 0 0.
+  // Not virtual: the reference's interface has no such call.
+  void IrradianceBatch(const std::vector<core::Point3>& points, const std::vector<core::Vec3>& normals,
+                       std::vector<core::Vec3>& out, int samples, int max_depth, uint64_t seed,
+                       const std::vector<uint32_t>* ids = nullptr, int first_sample = 0,
+                       std::vector<uint32_t>* segments = nullptr) const {
+    if (normals.size() != points.size()) throw std::invalid_argument("IrradianceBatch: one normal per point");
+    out.resize(points.size());
+    if (segments) segments->resize(points.size());
+    if (points.empty()) return;
+    if (ids && ids->size() != points.size()) throw std::invalid_argument("IrradianceBatch: one id per point");
+    std::vector<rtx_ray> s(points.size());
+    for (size_t i = 0; i < points.size(); i++)
+      for (int k = 0; k < 3; k++) s[i].origin[k] = points[i][k], s[i].direction[k] = normals[i][k];
+    rtx_radiance_params p{};
+    p.spp = samples, p.max_depth = max_depth, p.first_sample = first_sample, p.precision = precision_, p.seed = seed;
+    std::vector<double> rgb(3 * points.size());
+    if (rtx_irradiance(dev_, s.data(), ids ? ids->data() : nullptr, s.size(), &p, rgb.data(),
+                       segments ? segments->data() : nullptr) != RTX_OK)
+      throw std::runtime_error(std::string("rtx_irradiance: ") + rtx_last_error());
+    for (size_t i = 0; i < points.size(); i++) out[i] = core::Vec3(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]);
+  }
+
   rtx_scene* device_scene() const { return dev_; }
   const RtxScene& flat() const { return flat_; }
 
