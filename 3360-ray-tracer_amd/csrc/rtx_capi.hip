@@ -27,6 +27,7 @@
 #include "rtx_p3.h"
 #include "rtx_radiance.h"
 #include "rtx_irradiance.h"
+#include "rtx_direct.h"
 #include "rtx_scan.h"
 
 using namespace rtxd;
@@ -248,6 +249,10 @@ struct rtx_scene {
   // segment totals on the device, the rays through `rays`)
   DevBuf rad_L, rad_segs, rad_carry, rad_ids, rad_out, rad_oseg;
   HostBuf rad_host;
+  // rtx_direct (rtx_direct.h): the emitters' primitive indices, fixed at create (kept on the host
+  // too), and their cumulative areas, rebuilt on the device after every update; none: no buffers
+  std::vector<uint32_t> emit_idx;
+  DevBuf emit_prim, emit_cum;
   DevBuf patch_q;              // adaptive early output: the pixels still sampling when it went
   // AOVs and the denoiser (rtx_denoise.h): the f64 AOVs of rtx_aov / a film's first denoise, the
   // host entry points' staged inputs, an adaptive film's variance, and the filter's f32 working
@@ -280,7 +285,8 @@ struct rtx_scene {
     for (DevBuf* b : {&nodes, &prims, &mats, &texs, &images, &fnodes, &tri_n, &px_sum, &px_mean, &px_m2, &px_samples,
                       &px_conv, &lbuf, &queue[0], &queue[1], &counters, &out_rgb, &out_spp, &rays, &hits, &p3_scratch,
                       &p3_body, &calib_rgb, &patch_q, &aov_f64, &dn_in, &dn_var, &dn_work[0], &dn_work[1], &dn_guide,
-                      &dn_alb, &occ, &rad_L, &rad_segs, &rad_carry, &rad_ids, &rad_out, &rad_oseg})
+                      &dn_alb, &occ, &rad_L, &rad_segs, &rad_carry, &rad_ids, &rad_out, &rad_oseg,
+                      &emit_prim, &emit_cum})
       b->release();
     rad_host.release();
     for (auto& t : texels) t.release();
@@ -808,7 +814,34 @@ int launch_irradiance(rtx_scene* sc, const RadianceChunk& A, hipStream_t s) {
   HIPC(hipGetLastError());
   return RTX_OK;
 }
-// the checks rtx_radiance*, rtx_irradiance* and rtx_internal_irradiance_rays share, in the documented order
+// ---- direct-lighting queries (rtx_direct.h) ----
+EmitterTable emitter_table(const rtx_scene* sc) {
+  return EmitterTable{sc->emit_prim.as<uint32_t>(), sc->emit_cum.as<double>(), (int64_t)sc->emit_idx.size()};
+}
+// The emitters' areas and their running sum from the live primitives, on `s`: at create, and at
+// the end of every in-place update.  A scene without emitters launches nothing.
+int emitters_rebuild(rtx_scene* sc, hipStream_t s) {
+  const EmitterTable E = emitter_table(sc);
+  if (E.n <= 0) return RTX_OK;
+  hipLaunchKernelGGL(k_emitter_area, dim3((unsigned)((E.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
+                     sc->prims.as<rtx_prim>(), E);
+  HIPC(hipGetLastError());
+  hipLaunchKernelGGL(k_emitter_scan, dim3(1), dim3(kBlock), 0, s, E);
+  HIPC(hipGetLastError());
+  return RTX_OK;
+}
+// launch_radiance's launch of k_direct: A.rays are surfels
+template <int STACK, bool FAST>
+int launch_direct(rtx_scene* sc, const RadianceChunk& A, hipStream_t s) {
+  hipLaunchKernelGGL((k_direct<STACK, FAST>), dim3((A.slots + kBlock - 1) / kBlock), dim3(kBlock),
+                     stack_lds_bytes(STACK), s, sc->S, emitter_table(sc), A);
+  HIPC(hipGetLastError());
+  return RTX_OK;
+}
+// what a chunk's slots hold (radiance_on): a path from a caller's ray, a path from a surfel's
+// hemisphere sample, or a surfel's emitter sample
+enum SlotKind { kSlotRadiance = 0, kSlotIrradiance = 1, kSlotDirect = 2 };
+// the checks rtx_radiance*, rtx_irradiance*, rtx_direct* and their test hooks share, in the documented order
 int radiance_check(const rtx_scene* sc, const rtx_radiance_params* prm, const void* rays, const void* out) {
   if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
   if (!prm) return fail(RTX_ERR_INVALID, "NULL argument");
@@ -824,10 +857,12 @@ int radiance_check(const rtx_scene* sc, const rtx_radiance_params* prm, const vo
 // n > 0 rays on device buffers, in chunks of at most `cap` slots (ray x sample): whole rays per
 // chunk, or, when one ray's samples exceed the cap, one ray at a time in runs of `cap` samples
 // whose partial sum k_radiance_sum carries.  id_base: the pixel key of d_rays[0] when d_ids is
-// null (the host entry point's batches).  irr: d_rays are surfels and the slots are k_irradiance's
-// (rtx_irradiance*); the chunking, the scratch and the sum are the same.
+// null (the host entry point's batches).  what: for kSlotIrradiance and kSlotDirect d_rays are
+// surfels and the slots are k_irradiance's (rtx_irradiance*) or k_direct's (rtx_direct*: a
+// slot's "segments" are its visibility, 0 or 1); the chunking, the scratch and the sum are the same.
 int radiance_on(rtx_scene* sc, const rtx_ray* d_rays, const uint32_t* d_ids, uint64_t id_base, int64_t n,
-                const rtx_radiance_params* prm, double* d_out, uint32_t* d_segs, hipStream_t s, bool irr = false) {
+                const rtx_radiance_params* prm, double* d_out, uint32_t* d_segs, hipStream_t s,
+                SlotKind what = kSlotRadiance) {
   const int64_t tuned = g_radiance_chunk.load();
   const int64_t cap = std::min<int64_t>(tuned > 0 ? tuned : kRadianceSlots, kRadianceSlotsMax);
   const int64_t spp = prm->spp;
@@ -852,7 +887,10 @@ int radiance_on(rtx_scene* sc, const rtx_ray* d_rays, const uint32_t* d_ids, uin
       A.slots = (uint32_t)(nr * K), A.K = (uint32_t)K;
       A.s0 = (int32_t)(prm->first_sample + k0), A.max_depth = prm->max_depth, A.seed = prm->seed;
       A.L = sc->rad_L.as<double>(), A.segs = sc->rad_segs.as<uint32_t>();
-      if (irr) {
+      if (what == kSlotDirect) {
+        if (fast) rc = st == 32 ? launch_direct<32, true>(sc, A, s) : launch_direct<64, true>(sc, A, s);
+        else rc = st == 32 ? launch_direct<32, false>(sc, A, s) : launch_direct<64, false>(sc, A, s);
+      } else if (what == kSlotIrradiance) {
         if (fast) rc = st == 32 ? launch_irradiance<32, true>(sc, A, s) : launch_irradiance<64, true>(sc, A, s);
         else rc = st == 32 ? launch_irradiance<32, false>(sc, A, s) : launch_irradiance<64, false>(sc, A, s);
       } else if (fast) rc = st == 32 ? launch_radiance<32, true>(sc, A, s) : launch_radiance<64, true>(sc, A, s);
@@ -1347,6 +1385,16 @@ int rtx_scene_create(int device, const rtx_scene_desc* d, rtx_scene** out) {
       if ((rc = upload(sc->f4_order, forder.data(), forder.size(), s))) return rc;
     }
   }
+  // the emitter table (rtx_direct.h): the primitives whose material is a DiffuseLight, in the
+  // order of the primitive array; kinds and materials stay (an update changes geometry), so the
+  // list is final and only the areas are rebuilt
+  for (int64_t i = 0; i < d->n_prims; i++)
+    if (d->materials[d->prims[i].material].kind == RTX_MAT_DIFFUSE_LIGHT) sc->emit_idx.push_back((uint32_t)i);
+  if (!sc->emit_idx.empty()) {
+    if ((rc = upload(sc->emit_prim, sc->emit_idx.data(), sc->emit_idx.size(), s))) return rc;
+    if ((rc = sc->emit_cum.reserve(sc->emit_idx.size() * sizeof(double)))) return rc;
+    if ((rc = emitters_rebuild(sc.get(), s))) return rc;
+  }
   const int n_global = plan.n_global;
   HIPC(hipStreamSynchronize(s));
   DScene& S = sc->S;
@@ -1426,6 +1474,8 @@ int update_and_refit(rtx_scene* sc, int64_t first, int64_t count, const rtx_prim
   for (size_t k = 0; k + 1 < sc->f4_lvl.size(); k++)
     HIPC(rtxrefit::refit_f4(sc->fnodes.as<F4Node>(), sc->fast_box.as<float>(),
                             sc->f4_order.as<uint32_t>() + sc->f4_lvl[k], sc->f4_lvl[k + 1] - sc->f4_lvl[k], s));
+  int rc;
+  if ((rc = emitters_rebuild(sc, s))) return rc;  // the emitters' areas follow the new geometry
   sc->epoch++;
   return RTX_OK;
 }
@@ -1614,9 +1664,9 @@ int rtx_radiance_device(rtx_scene* sc, const rtx_ray* d_rays, const uint32_t* d_
 // The host entry point works in batches of kRadianceHostRays rays: the caller's rays and ids are
 // copied into pinned memory, traced, and the results copied back out of it.
 constexpr size_t kRadianceHostRays = (size_t)1 << 20;
-// (shared with rtx_irradiance, irr: the rays are surfels)
+// (shared with rtx_irradiance and rtx_direct, whose rays are surfels)
 static int radiance_host(rtx_scene* sc, const rtx_ray* rays, const uint32_t* ids, size_t n,
-                         const rtx_radiance_params* prm, double* out_rgb, uint32_t* out_segments, bool irr) {
+                         const rtx_radiance_params* prm, double* out_rgb, uint32_t* out_segments, SlotKind what) {
   int rc;
   if ((rc = radiance_check(sc, prm, rays, out_rgb))) return rc;
   if (n == 0) return RTX_OK;
@@ -1640,7 +1690,7 @@ static int radiance_host(rtx_scene* sc, const rtx_ray* rays, const uint32_t* ids
       HIPC(hipMemcpyAsync(sc->rad_ids.p, pin + off_ids, nb * sizeof(uint32_t), hipMemcpyHostToDevice, sc->stream));
     }
     if ((rc = radiance_on(sc, sc->rays.as<rtx_ray>(), ids ? sc->rad_ids.as<uint32_t>() : nullptr, (uint64_t)b0,
-                          (int64_t)nb, prm, sc->rad_out.as<double>(), sc->rad_oseg.as<uint32_t>(), sc->stream, irr)))
+                          (int64_t)nb, prm, sc->rad_out.as<double>(), sc->rad_oseg.as<uint32_t>(), sc->stream, what)))
       return rc;
     HIPC(hipMemcpyAsync(pin + off_rgb, sc->rad_out.p, nb * 3 * sizeof(double), hipMemcpyDeviceToHost, sc->stream));
     if (out_segments)
@@ -1653,7 +1703,7 @@ static int radiance_host(rtx_scene* sc, const rtx_ray* rays, const uint32_t* ids
 }
 int rtx_radiance(rtx_scene* sc, const rtx_ray* rays, const uint32_t* ids, size_t n, const rtx_radiance_params* prm,
                  double* out_rgb, uint32_t* out_segments) {
-  return radiance_host(sc, rays, ids, n, prm, out_rgb, out_segments, false);
+  return radiance_host(sc, rays, ids, n, prm, out_rgb, out_segments, kSlotRadiance);
 }
 
 // ---- irradiance queries (rtx_irradiance.h): rtx_radiance's checks, chunks and staging ----
@@ -1664,12 +1714,12 @@ int rtx_irradiance_device(rtx_scene* sc, const rtx_ray* d_surfels, const uint32_
   if (n == 0) return RTX_OK;
   HIPC(hipSetDevice(sc->device));
   return radiance_on(sc, d_surfels, d_ids, 0, (int64_t)n, prm, d_out_rgb, d_out_segments,
-                     stream ? (hipStream_t)stream : sc->stream, true);
+                     stream ? (hipStream_t)stream : sc->stream, kSlotIrradiance);
 }
 
 int rtx_irradiance(rtx_scene* sc, const rtx_ray* surfels, const uint32_t* ids, size_t n,
                    const rtx_radiance_params* prm, double* out_rgb, uint32_t* out_segments) {
-  return radiance_host(sc, surfels, ids, n, prm, out_rgb, out_segments, true);
+  return radiance_host(sc, surfels, ids, n, prm, out_rgb, out_segments, kSlotIrradiance);
 }
 
 // Test hook (not in rtx.h): the depth-0 segments rtx_irradiance traces for the same arguments
@@ -1698,6 +1748,84 @@ extern "C" int rtx_internal_irradiance_rays(rtx_scene* sc, const rtx_ray* surfel
   HIPC(hipGetLastError());
   HIPC(hipMemcpyAsync(out, sc->rad_L.p, bytes, hipMemcpyDeviceToHost, sc->stream));
   HIPC(hipStreamSynchronize(sc->stream));
+  return RTX_OK;
+}
+
+// ---- direct-lighting queries (rtx_direct.h): rtx_radiance's checks, chunks and staging ----
+int rtx_direct_device(rtx_scene* sc, const rtx_ray* d_surfels, const uint32_t* d_ids, size_t n,
+                      const rtx_radiance_params* prm, double* d_out_rgb, uint32_t* d_out_visible, void* stream) {
+  int rc;
+  if ((rc = radiance_check(sc, prm, d_surfels, d_out_rgb))) return rc;
+  if (n == 0) return RTX_OK;
+  HIPC(hipSetDevice(sc->device));
+  return radiance_on(sc, d_surfels, d_ids, 0, (int64_t)n, prm, d_out_rgb, d_out_visible,
+                     stream ? (hipStream_t)stream : sc->stream, kSlotDirect);
+}
+
+int rtx_direct(rtx_scene* sc, const rtx_ray* surfels, const uint32_t* ids, size_t n, const rtx_radiance_params* prm,
+               double* out_rgb, uint32_t* out_visible) {
+  return radiance_host(sc, surfels, ids, n, prm, out_rgb, out_visible, kSlotDirect);
+}
+
+int rtx_scene_emitters(const rtx_scene* sc, int64_t* count, double* area) {
+  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
+  if (!count && !area) return fail(RTX_ERR_INVALID, "NULL argument");
+  const int64_t n = (int64_t)sc->emit_idx.size();
+  if (count) *count = n;
+  if (area) {
+    *area = 0.0;
+    if (n > 0) {
+      HIPC(hipSetDevice(sc->device));
+      HIPC(hipStreamSynchronize(sc->stream));
+      HIPC(hipMemcpy(area, sc->emit_cum.as<double>() + (n - 1), sizeof(double), hipMemcpyDeviceToHost));
+    }
+  }
+  return RTX_OK;
+}
+
+// Test hook (not in rtx.h): the samples rtx_direct draws for the same arguments (seed,
+// first_sample and spp of prm are read; the rest is checked as there), n x spp x 9 doubles
+// (segment origin, y - x, the unshadowed contribution C), surfel major, made by the device
+// function k_direct calls (direct_sample, rtx_direct.h); all zero where nothing is traced.  Host
+// buffers.
+extern "C" int rtx_internal_direct_samples(rtx_scene* sc, const rtx_ray* surfels, const uint32_t* ids, size_t n,
+                                           const rtx_radiance_params* prm, double* out) {
+  int rc;
+  if ((rc = radiance_check(sc, prm, surfels, out))) return rc;
+  if (n == 0) return RTX_OK;
+  if (n > (size_t)kRadianceSlotsMax || (int64_t)n * prm->spp > kRadianceSlotsMax)
+    return fail(RTX_ERR_INVALID, "direct samples: too many samples for one call");
+  HIPC(hipSetDevice(sc->device));
+  const uint32_t nslots = (uint32_t)(n * (size_t)prm->spp);
+  const size_t bytes = (size_t)nslots * 9 * sizeof(double);
+  if ((rc = sc->rays.reserve(n * sizeof(rtx_ray)))) return rc;
+  if ((rc = sc->rad_L.reserve(bytes))) return rc;
+  if (ids && (rc = sc->rad_ids.reserve(n * sizeof(uint32_t)))) return rc;
+  HIPC(hipMemcpyAsync(sc->rays.p, surfels, n * sizeof(rtx_ray), hipMemcpyHostToDevice, sc->stream));
+  if (ids) HIPC(hipMemcpyAsync(sc->rad_ids.p, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, sc->stream));
+  hipLaunchKernelGGL(k_direct_samples, dim3((nslots + kBlock - 1) / kBlock), dim3(kBlock), 0, sc->stream, sc->S,
+                     emitter_table(sc), sc->rays.as<rtx_ray>(), ids ? sc->rad_ids.as<uint32_t>() : nullptr, nslots,
+                     (uint32_t)prm->spp, prm->seed, prm->first_sample, sc->rad_L.as<double>());
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(out, sc->rad_L.p, bytes, hipMemcpyDeviceToHost, sc->stream));
+  HIPC(hipStreamSynchronize(sc->stream));
+  return RTX_OK;
+}
+
+// Test hook (not in rtx.h): the live emitter table copied back after everything queued on the
+// scene's stream, at most `cap` entries: each emitter's primitive index (the caller's own order,
+// as rtx_scene_update_prims counts it) and the inclusive cumulative areas.  Either may be NULL.
+extern "C" int rtx_internal_emitters(rtx_scene* sc, int64_t* prims_out, double* cum_out, int64_t cap) {
+  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
+  const int64_t n = std::min<int64_t>(std::max<int64_t>(0, cap), (int64_t)sc->emit_idx.size());
+  if (n == 0) return RTX_OK;
+  if (prims_out)
+    for (int64_t i = 0; i < n; i++) prims_out[i] = (int64_t)sc->emit_idx[(size_t)i];
+  if (cum_out) {
+    HIPC(hipSetDevice(sc->device));
+    HIPC(hipStreamSynchronize(sc->stream));
+    HIPC(hipMemcpy(cum_out, sc->emit_cum.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+  }
   return RTX_OK;
 }
 

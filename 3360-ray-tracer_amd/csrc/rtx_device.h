@@ -98,6 +98,9 @@ constexpr uint32_t kRngStreamAo = 0xA0000000u;  // no render kernel opens it (st
 // path's segments, the query's own included, shade from streams depth + 1 <= 2^31 (an int32
 // depth), below both constants; the camera ray is stream 0; and the AO pass's is another value.
 constexpr uint32_t kRngStreamIrr = 0xA1000000u;
+// The direct-lighting queries' emitter samples (rtx_direct.h): another value above every
+// segment's stream, so it collides with none of the above.
+constexpr uint32_t kRngStreamDirect = 0xA2000000u;
 __device__ __forceinline__ void philox_block(uint32_t blk, uint32_t sample, uint32_t pixel, uint32_t stream,
                                              uint32_t k0, uint32_t k1, double& u0, double& u1) {
   uint32_t c0 = blk, c1 = sample, c2 = pixel, c3 = stream;

@@ -58,6 +58,16 @@ class GpuRayIntegrator : public RayIntegrator {
                        std::vector<core::Vec3>& out, int samples, int max_depth, uint64_t seed,
                        const std::vector<uint32_t>* ids = nullptr, int first_sample = 0,
                        std::vector<uint32_t>* segments = nullptr) const;
+  // Direct-lighting query: out[i] = the light reaching points[i] straight from the scene's
+  // emitters, in IrradianceBatch's unit, from `samples` points per surfel drawn uniformly over the
+  // emitting area and weighted by the geometry term and the shadow segment's visibility
+  // (rtx_direct: keyed by (seed, ids ? ids[i] : i, first_sample + k)).  A zero or non-finite
+  // normal, and a scene without emitters, give 0 0 0.  visible, if given: the unoccluded samples
+  // per point.  Not part of the reference's RayIntegrator interface.
+  void DirectBatch(const std::vector<core::Point3>& points, const std::vector<core::Vec3>& normals,
+                   std::vector<core::Vec3>& out, int samples, uint64_t seed,
+                   const std::vector<uint32_t>* ids = nullptr, int first_sample = 0,
+                   std::vector<uint32_t>* visible = nullptr) const;
   rtx_scene* device_scene() const { return dev_; }
   // Replace primitives [first, first + prims.size()) of the device copy, in its own order (leaf
   // order for a BVH world), and refit its trees in place (rtx_scene_update_prims): kinds stay,

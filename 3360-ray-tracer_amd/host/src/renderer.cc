@@ -88,6 +88,28 @@ void GpuRayIntegrator::IrradianceBatch(const std::vector<core::Point3>& points, 
   for (size_t i = 0; i < points.size(); i++) out[i] = core::Vec3(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]);
 }
 
+// The light reaching each point straight from the scene's emitters (rtx_direct).
+void GpuRayIntegrator::DirectBatch(const std::vector<core::Point3>& points, const std::vector<core::Vec3>& normals,
+                                   std::vector<core::Vec3>& out, int samples, uint64_t seed,
+                                   const std::vector<uint32_t>* ids, int first_sample,
+                                   std::vector<uint32_t>* visible) const {
+  if (normals.size() != points.size()) throw std::invalid_argument("DirectBatch: one normal per point");
+  out.resize(points.size());
+  if (visible) visible->resize(points.size());
+  if (points.empty()) return;
+  if (ids && ids->size() != points.size()) throw std::invalid_argument("DirectBatch: one id per point");
+  std::vector<rtx_ray> s(points.size());
+  for (size_t i = 0; i < points.size(); i++)
+    for (int k = 0; k < 3; k++) s[i].origin[k] = points[i][k], s[i].direction[k] = normals[i][k];
+  rtx_radiance_params p{};
+  p.spp = samples, p.max_depth = 0, p.first_sample = first_sample, p.precision = precision_, p.seed = seed;
+  std::vector<double> rgb(3 * points.size());
+  check(rtx_direct(dev_, s.data(), ids ? ids->data() : nullptr, s.size(), &p, rgb.data(),
+                   visible ? visible->data() : nullptr),
+        "rtx_direct");
+  for (size_t i = 0; i < points.size(); i++) out[i] = core::Vec3(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]);
+}
+
 }  // namespace rt::integrator
 
 namespace rt::renderer {

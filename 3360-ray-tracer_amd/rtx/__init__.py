@@ -16,6 +16,7 @@ CAMERAS = os.path.join(REPO, "configs", "cameras.json")
 
 RTX_OK = 0
 RTX_SEAM_TMIN = float(np.float32(0.001))
+RTX_DIRECT_TMAX = float(np.float32(0.9999))  # where a direct-lighting shadow segment ends (rtx.h)
 MODES = {"wavefront": 0, "persistent": 1, "megakernel": 2}
 PRECISIONS = {"parity": 0, "fast": 1}
 RTX_FLAG_COUNT, RTX_FLAG_PARK, RTX_FLAG_NO_PARK, RTX_FLAG_GENERIC, RTX_FLAG_LEAF_STEP = 1, 2, 4, 8, 16
@@ -144,7 +145,7 @@ EXPORTS = ["rtx_abi_version", "rtx_last_error", "rtx_device_count", "rtx_scene_c
            "rtx_denoise_device", "rtx_film_denoise", "rtx_film_denoise_p3", "rtx_scene_update_prims",
            "rtx_scene_update_geometry_device", "rtx_scene_epoch", "rtx_bvh_refit_host", "rtx_film_reset",
            "rtx_occluded", "rtx_occluded_device", "rtx_ao", "rtx_ao_device", "rtx_radiance", "rtx_radiance_device",
-           "rtx_irradiance", "rtx_irradiance_device"]
+           "rtx_irradiance", "rtx_irradiance_device", "rtx_direct", "rtx_direct_device", "rtx_scene_emitters"]
 
 _lib = None
 
@@ -220,6 +221,9 @@ def lib():
             "rtx_radiance_device": ([vp, vp, vp, sz, C.POINTER(RadianceParams), vp, vp, vp], C.c_int),
             "rtx_irradiance": ([vp, vp, vp, sz, C.POINTER(RadianceParams), vp, vp], C.c_int),
             "rtx_irradiance_device": ([vp, vp, vp, sz, C.POINTER(RadianceParams), vp, vp, vp], C.c_int),
+            "rtx_direct": ([vp, vp, vp, sz, C.POINTER(RadianceParams), vp, vp], C.c_int),
+            "rtx_direct_device": ([vp, vp, vp, sz, C.POINTER(RadianceParams), vp, vp, vp], C.c_int),
+            "rtx_scene_emitters": ([vp, C.POINTER(C.c_int64), C.POINTER(C.c_double)], C.c_int),
         }
         for name, (args, res) in sig.items():
             f = getattr(L, name)
@@ -473,6 +477,47 @@ class DeviceScene:
                                            C.byref(p), C.c_void_p(d_out),
                                            C.c_void_p(d_segments) if d_segments else None,
                                            C.c_void_p(stream) if stream else None), "rtx_irradiance_device")
+
+    def direct(self, points, normals, samples, seed=1234, ids=None, first_sample=0, precision="parity", visible=False):
+        """Direct-lighting query (rtx_direct): (n, 3), the light reaching each point straight from
+        the scene's emitters, in irradiance()'s unit (the two add and compare directly), from
+        `samples` points per surfel drawn uniformly over the emitting area, each weighted by the
+        geometry term and by the visibility of its shadow segment (occluded() on (RTX_SEAM_TMIN,
+        RTX_DIRECT_TMAX)).  Sample k of point i draws from (seed, pixel = ids[i] or i,
+        sample = first_sample + k) and equals direct_samples()'s C times that visibility.  A zero
+        or non-finite normal, and a scene without emitters, give 0 0 0.  visible=True: also the
+        (n,) uint32 samples per point whose segment was traced and found unoccluded."""
+        surfels = _surfels(points, normals)
+        n = len(surfels)
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+            if len(ids) != n:
+                raise ValueError("direct: one id per point")
+        out = np.zeros((n, 3))
+        vis = np.zeros(n, np.uint32) if visible else None
+        p = self._radiance_params(samples, 0, seed, first_sample, precision)
+        _check(lib().rtx_direct(self.h, surfels.ctypes.data_as(C.c_void_p),
+                                None if ids is None else ids.ctypes.data_as(C.c_void_p), n, C.byref(p),
+                                out.ctypes.data_as(C.c_void_p),
+                                None if vis is None else vis.ctypes.data_as(C.c_void_p)), "rtx_direct")
+        return (out, vis) if visible else out
+
+    def direct_device(self, d_surfels, n, d_out, samples, seed=1234, first_sample=0, precision="parity", d_ids=0,
+                      d_visible=0, stream=0):
+        """The same on device buffers (rtx_direct_device): d_surfels names n x 6 doubles (point,
+        normal), d_out n x 3 doubles, d_ids n uint32 (0: the point's index), d_visible n uint32
+        (0: none), e.g. torch tensors' data_ptr().  Asynchronous."""
+        p = self._radiance_params(samples, 0, seed, first_sample, precision)
+        _check(lib().rtx_direct_device(self.h, C.c_void_p(d_surfels), C.c_void_p(d_ids) if d_ids else None, n,
+                                       C.byref(p), C.c_void_p(d_out), C.c_void_p(d_visible) if d_visible else None,
+                                       C.c_void_p(stream) if stream else None), "rtx_direct_device")
+
+    def emitters(self):
+        """(count, area): the scene's emitters (primitives with a DiffuseLight material) and their
+        total area in the live scene (rtx_scene_emitters); (0, 0.0) without emitters."""
+        n, a = C.c_int64(0), C.c_double(0.0)
+        _check(lib().rtx_scene_emitters(self.h, C.byref(n), C.byref(a)), "rtx_scene_emitters")
+        return n.value, a.value
 
     def _ao_args(self, cam, samples, radius, seed, tile, stripes, precision):
         p = RenderParams()
@@ -758,6 +803,39 @@ def irradiance_rays(scene, points, normals, samples, seed, ids=None, first_sampl
     _check(f(scene.h, surfels.ctypes.data_as(C.c_void_p), None if ids is None else ids.ctypes.data_as(C.c_void_p), n,
              C.byref(p), out.ctypes.data_as(C.c_void_p)), "rtx_internal_irradiance_rays")
     return out
+
+
+def direct_samples(scene, points, normals, samples, seed, ids=None, first_sample=0):
+    """Test hook (rtx_internal_direct_samples, not in rtx.h): the samples DeviceScene.direct draws
+    for the same arguments, (n, samples, 9): the shadow segment's origin, y - x, and the unshadowed
+    contribution C, from the device function the kernel calls; all zero where nothing is traced."""
+    surfels = _surfels(points, normals)
+    n = len(surfels)
+    if ids is not None:
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        if len(ids) != n:
+            raise ValueError("direct: one id per point")
+    f = lib().rtx_internal_direct_samples
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RadianceParams), C.c_void_p]
+    f.restype = C.c_int
+    p = DeviceScene._radiance_params(samples, 0, seed, first_sample, "parity")
+    out = np.zeros((n, samples, 9))
+    _check(f(scene.h, surfels.ctypes.data_as(C.c_void_p), None if ids is None else ids.ctypes.data_as(C.c_void_p), n,
+             C.byref(p), out.ctypes.data_as(C.c_void_p)), "rtx_internal_direct_samples")
+    return out
+
+
+def emitter_table(scene):
+    """Test hook (rtx_internal_emitters, not in rtx.h): the live emitter table, (prims, cum): each
+    emitter's primitive index (int64, the scene's own order as update_prims counts it) and the
+    inclusive cumulative areas (float64), whose last entry is emitters()'s area."""
+    n = scene.emitters()[0]
+    prims, cum = np.zeros(n, np.int64), np.zeros(n, np.float64)
+    f = lib().rtx_internal_emitters
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    f.restype = C.c_int
+    _check(f(scene.h, prims.ctypes.data_as(C.c_void_p), cum.ctypes.data_as(C.c_void_p), n), "rtx_internal_emitters")
+    return prims, cum
 
 
 def radiance_chunk(slots=0):

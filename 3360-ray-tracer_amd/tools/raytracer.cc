@@ -4,7 +4,7 @@
 //             [--mode wavefront|persistent|megakernel] [--precision parity|fast]
 //             [--mk-adaptive MIN:THRESHOLD] [--gpus N]
 //             [--chunks N] [--preview PREFIX] [--checkpoint FILE] [--resume FILE] [--denoise]
-//             [--ao N[,RADIUS]] [--irradiance N[,DEPTH]] > out.ppm
+//             [--ao N[,RADIUS]] [--irradiance N[,DEPTH]] [--direct N] > out.ppm
 // --gpus N renders one frame over N GPUs (interleaved row stripes, one host thread per GPU,
 // one gathered framebuffer and P3 output; identical pixels for every N); --devices 0,2,3
 // names the devices (a device may repeat: several streams on one GPU).
@@ -25,6 +25,10 @@
 // over the hemisphere about the hit's normal, keyed by the global pixel; default DEPTH the
 // preset's max depth, or --depth; black where the pixel's ray misses) as a P3 PPM through the
 // device encoder; --seed and --precision apply.
+// --direct N writes the direct-lighting pass instead of a render (rtx_direct: at each pixel's
+// first hit, the light arriving straight from the scene's emitters, from N points sampled on the
+// emitters and their shadow segments, keyed by the global pixel; black where the pixel's ray
+// misses) as a P3 PPM through the device encoder; --seed and --precision apply.
 // --mk-adaptive selects the AdaptiveSampler (sampler.h:44-82) for --mode megakernel,
 // with max_samples = the preset's (or --spp) samples.
 // Defaults follow main.cc: preset "default" (fallback when unknown), the Cornell box
@@ -54,6 +58,8 @@ int main(int argc, char** argv) {
   int mk_min = -1, gpus = 1, chunks = 0, ao_samples = 0;
   int irr_samples = 0, irr_depth = -1;  // --irradiance (depth -1: the preset's)
   bool irr = false;
+  int direct_samples = 0;  // --direct
+  bool direct = false;
   double ao_radius = 0.0;  // 0: a quarter of the scene's bounding-box diagonal
   std::string preview, checkpoint, resume;
   float mk_thr = 0.0f;
@@ -98,6 +104,14 @@ int main(int argc, char** argv) {
       if (c != std::string::npos) irr_depth = std::atoi(v.substr(c + 1).c_str());
       if (irr_samples < 1 || (c != std::string::npos && irr_depth < 0)) {
         std::cerr << "--irradiance expects N[,DEPTH] with N >= 1 and DEPTH >= 0\n";
+        return 2;
+      }
+    }
+    else if (a == "--direct") {
+      direct = true;
+      direct_samples = std::atoi(next().c_str());
+      if (direct_samples < 1) {
+        std::cerr << "--direct expects N >= 1\n";
         return 2;
       }
     }
@@ -179,7 +193,7 @@ int main(int argc, char** argv) {
         throw std::runtime_error(std::string("rtx_encode_p3: ") + rtx_last_error());
       std::cout.write(bytes.data(), (std::streamsize)len);
       std::clog << "AO: " << ao_samples << " samples, radius " << ao_radius << "\n";
-    } else if (irr) {
+    } else if (irr || direct) {
       integrator::GpuRayIntegrator integ(world.get(), devices.empty() ? 0 : devices[0],
                                          precision == "fast" ? RTX_PREC_FAST : RTX_PREC_PARITY);
       const rtx_camera& dc = cam.device();
@@ -208,17 +222,24 @@ int main(int argc, char** argv) {
           rays[i].origin[k] = hits[i].hit ? hits[i].p[k] : 0.0, rays[i].direction[k] = hits[i].hit ? hits[i].normal[k] : 0.0;
       }
       rtx_radiance_params rp{};
-      rp.spp = irr_samples, rp.max_depth = irr_depth >= 0 ? irr_depth : md, rp.first_sample = 0;
+      rp.spp = direct ? direct_samples : irr_samples, rp.max_depth = irr_depth >= 0 ? irr_depth : md, rp.first_sample = 0;
       rp.precision = integ.precision(), rp.seed = seed;
       std::vector<double> rgb(3 * npix);
-      if (rtx_irradiance(integ.device_scene(), rays.data(), ids.data(), npix, &rp, rgb.data(), nullptr) != RTX_OK)
+      int64_t n_emitters = 0;
+      if (direct) {
+        if (rtx_direct(integ.device_scene(), rays.data(), ids.data(), npix, &rp, rgb.data(), nullptr) != RTX_OK)
+          throw std::runtime_error(std::string("rtx_direct: ") + rtx_last_error());
+        if (rtx_scene_emitters(integ.device_scene(), &n_emitters, nullptr) != RTX_OK)
+          throw std::runtime_error(std::string("rtx_scene_emitters: ") + rtx_last_error());
+      } else if (rtx_irradiance(integ.device_scene(), rays.data(), ids.data(), npix, &rp, rgb.data(), nullptr) != RTX_OK)
         throw std::runtime_error(std::string("rtx_irradiance: ") + rtx_last_error());
       std::string bytes(rtx_p3_max_bytes(W, H), '\0');
       size_t len = 0;
       if (rtx_encode_p3(integ.device_scene(), rgb.data(), W, H, bytes.data(), bytes.size(), &len) != RTX_OK)
         throw std::runtime_error(std::string("rtx_encode_p3: ") + rtx_last_error());
       std::cout.write(bytes.data(), (std::streamsize)len);
-      std::clog << "irradiance: " << irr_samples << " samples, depth " << rp.max_depth << "\n";
+      if (direct) std::clog << "direct: " << direct_samples << " samples, " << n_emitters << " emitters\n";
+      else std::clog << "irradiance: " << irr_samples << " samples, depth " << rp.max_depth << "\n";
     } else if (mode == "megakernel") {
       integrator::DefaultSampler fixed_sampler(ns);
       integrator::AdaptiveSampler adaptive_sampler(mk_min, ns, mk_thr);

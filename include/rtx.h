@@ -551,6 +551,50 @@ int rtx_irradiance_device(rtx_scene* scene, const rtx_ray* d_surfels, const uint
                           const rtx_radiance_params* params, double* d_out_rgb, uint32_t* d_out_segments,
                           void* stream);
 
+/* ---- direct-lighting queries (DESIGN.md "Direct-lighting queries") ---------------------------
+ * How much light reaches these surface points straight from the scene's emitters?  The radiance
+ * and irradiance queries find a light only when a path runs into it; this one samples the lights.
+ * An emitter is a primitive whose material is RTX_MAT_DIFFUSE_LIGHT (any primitive kind; emission
+ * is two-sided).  The scene keeps a table of them with their cumulative areas, built on the
+ * device at rtx_scene_create and again by every rtx_scene_update_*.
+ * Surfels are rtx_irradiance's (origin x, direction the surface normal, any positive finite
+ * length); rtx_radiance_params is read as there, spp being the samples per point, and max_depth
+ * is checked and otherwise ignored.  For surfel i and sample k in [0, spp), three numbers u0, u1,
+ * u2 from a Philox stream of its own keyed by (seed, pixel = ids ? ids[i] : (uint32_t)i,
+ * sample = first_sample + k) give:
+ *   the emitter: the first whose cumulative area exceeds u0 * A (A: the total emitting area), so
+ *     the points are uniform over all emitting area (not weighted by power);
+ *   the point y on it: rect: linear in u1, u2; triangle: s = sqrt(u1),
+ *     y = (1 - s) a + s (1 - u2) b + s u2 c; sphere: z = 1 - 2 u1, phi = 2 pi u2 over the whole
+ *     sphere (the far side is rejected by the sphere's own occlusion);
+ *   the unshadowed contribution C = Le(y) max(0, n_x . w) |n_y . w| A / (pi |y - x|^2), w the unit
+ *     vector from x to y, Le and n_y from the hit record a path reaching y would build (textured
+ *     lights included);
+ *   the visibility V: 1 iff rtx_occluded finds nothing on (RTX_SEAM_TMIN, RTX_DIRECT_TMAX) of the
+ *     segment (x, y - x) with the walk of `precision`.  The margin below 1 keeps the emitter out of
+ *     its own shadow ray; a blocker within 1e-4 of the segment's length from the light is ignored.
+ * out_rgb: 3 doubles per surfel, the in-order sum of C V (from 0) times 1 / (double)(float)spp.
+ * Its mean estimates (1 / pi) * the integral of the emitters' radiance times cos(theta) over the
+ * hemisphere: rtx_irradiance's unit, so the two compare and add directly.
+ * out_visible (may be NULL): per surfel, the samples whose shadow segment was traced and found
+ * unoccluded.  A sample is 0 and traces nothing when the scene has no emitters or no emitting
+ * area, the normal is degenerate (rtx_irradiance's rule), |y - x|^2 is not > 0 or not finite, or
+ * C has no positive component (a light facing away or seen edge-on).
+ * Arguments are checked in rtx_radiance's order and with its messages before the scene or a
+ * device is touched; then n == 0 returns RTX_OK.  One call at a time per scene. */
+#define RTX_DIRECT_TMAX ((double)0.9999f)
+/* Host buffers, staged through pinned memory in batches; returns when the outputs are written. */
+int rtx_direct(rtx_scene* scene, const rtx_ray* surfels, const uint32_t* ids, size_t n,
+               const rtx_radiance_params* params, double* out_rgb, uint32_t* out_visible);
+/* Device buffers; asynchronous on stream (NULL = the scene's stream). */
+int rtx_direct_device(rtx_scene* scene, const rtx_ray* d_surfels, const uint32_t* d_ids, size_t n,
+                      const rtx_radiance_params* params, double* d_out_rgb, uint32_t* d_out_visible,
+                      void* stream);
+/* The live emitter table: the number of emitters and their total area A (0 and 0.0 for a scene
+ * without emitters), after everything queued on the scene's stream.  Either output may be NULL,
+ * not both. */
+int rtx_scene_emitters(const rtx_scene* scene, int64_t* count, double* area);
+
 enum { RTX_DENOISE_DEMODULATE = 1 }; /* filter colour / max(albedo, 1e-3), multiply back at the end */
 typedef struct {
   int32_t iterations; /* 0..8; iteration k filters 5 x 5 taps at step 2^k; 0 copies the input */

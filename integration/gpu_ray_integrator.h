@@ -117,6 +117,33 @@ class GpuRayIntegrator : public RayIntegrator {
     for (size_t i = 0; i < points.size(); i++) out[i] = core::Vec3(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]);
   }
 
+  // Direct-lighting query: out[i] = the light reaching points[i] straight from the scene's
+  // emitters, in IrradianceBatch's unit (the two add), from `samples` points per surfel drawn
+  // uniformly over the emitting area and weighted by the geometry term and the visibility of the
+  // shadow segment (rtx_direct: keyed by (seed, ids ? ids[i] : i, first_sample + k)).  A zero or
+  // non-finite normal, and a scene without emitters, give 0 0 0.  visible, if given: the
+  // unoccluded samples per point.  Not virtual: the reference's interface has no such call.
+  void DirectBatch(const std::vector<core::Point3>& points, const std::vector<core::Vec3>& normals,
+                   std::vector<core::Vec3>& out, int samples, uint64_t seed,
+                   const std::vector<uint32_t>* ids = nullptr, int first_sample = 0,
+                   std::vector<uint32_t>* visible = nullptr) const {
+    if (normals.size() != points.size()) throw std::invalid_argument("DirectBatch: one normal per point");
+    out.resize(points.size());
+    if (visible) visible->resize(points.size());
+    if (points.empty()) return;
+    if (ids && ids->size() != points.size()) throw std::invalid_argument("DirectBatch: one id per point");
+    std::vector<rtx_ray> s(points.size());
+    for (size_t i = 0; i < points.size(); i++)
+      for (int k = 0; k < 3; k++) s[i].origin[k] = points[i][k], s[i].direction[k] = normals[i][k];
+    rtx_radiance_params p{};
+    p.spp = samples, p.max_depth = 0, p.first_sample = first_sample, p.precision = precision_, p.seed = seed;
+    std::vector<double> rgb(3 * points.size());
+    if (rtx_direct(dev_, s.data(), ids ? ids->data() : nullptr, s.size(), &p, rgb.data(),
+                   visible ? visible->data() : nullptr) != RTX_OK)
+      throw std::runtime_error(std::string("rtx_direct: ") + rtx_last_error());
+    for (size_t i = 0; i < points.size(); i++) out[i] = core::Vec3(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]);
+  }
+
   rtx_scene* device_scene() const { return dev_; }
   const RtxScene& flat() const { return flat_; }
 
