@@ -1,6 +1,9 @@
-// rtx_capi.hip — C ABI (include/rtx.h) over the HIP kernels: scene upload, IntersectBatch,
-// full-path render.  gfx950 only; no CPU compute path and no fallback: a missing device or a
-// HIP error is returned as RTX_ERR_* with a message in rtx_last_error().
+// rtx_capi.hip — C ABI (include/rtx.h) over the HIP kernels: scene upload and in-place updates,
+// the frame renderer (full-path render, films, the denoiser's filter entry points, P3 encoding).
+// The ray-query entry points (rtx_intersect*, rtx_occluded*, rtx_ao*, rtx_aov*, rtx_radiance*,
+// rtx_irradiance*, rtx_direct*) are rtx_queries.hip; both units share rtx_host.h.  gfx950 only; no
+// CPU compute path and no fallback: a missing device or a HIP error is returned as RTX_ERR_* with
+// a message in rtx_last_error().
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,21 +19,13 @@
 #include <thread>
 #include <vector>
 
-#include "rtx.h"
-#include "rtx_bounds.h"
+#include "rtx_host.h"
 #include "rtx_refit.h"
-#define RTX_DENOISE_AOV_KERNELS  // this translation unit holds k_aov (it needs the trace kernels)
 #include "rtx_denoise.h"
 #include "rtx_film.h"
 #include "rtx_frame_kernels.h"
-#include "rtx_occlusion.h"
 #include "rtx_p3.h"
-#include "rtx_radiance.h"
-#include "rtx_irradiance.h"
-#include "rtx_direct.h"
 #include "rtx_scan.h"
-
-using namespace rtxd;
 
 // The PARK instantiations of k_persistent are compiled in rtx_park.hip (RTX_PARK_TU).
 namespace rtxd {
@@ -51,67 +46,7 @@ RTX_PARK_TRI_INSTANCES(RTX_PARK_TRI_EXTERN)
 }  // namespace rtxd
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-
-#define HIPC(expr)                                                                                   \
-  do {                                                                                               \
-    hipError_t e_ = (expr);                                                                          \
-    if (e_ != hipSuccess)                                                                            \
-      return fail(RTX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_) + " (" __FILE__ ":" + \
-                                   std::to_string(__LINE__) + ")");                                  \
-  } while (0)
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t n = 0;
-  int reserve(size_t bytes) {
-    if (bytes <= n) return RTX_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr, n = 0;
-    if (bytes == 0) return RTX_OK;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) return fail(RTX_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    n = bytes;
-    return RTX_OK;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr, n = 0;
-  }
-  template <class T>
-  T* as() const {
-    return (T*)p;
-  }
-};
-
-struct HostBuf {  // pinned host staging (grow-only)
-  void* p = nullptr;
-  size_t n = 0;
-  int reserve(size_t bytes) {
-    if (bytes <= n) return RTX_OK;
-    if (p) (void)hipHostFree(p);
-    p = nullptr, n = 0;
-    if (bytes == 0) return RTX_OK;
-    hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocDefault);
-    if (e != hipSuccess) return fail(RTX_ERR_NOMEM, std::string("hipHostMalloc: ") + hipGetErrorString(e));
-    n = bytes;
-    return RTX_OK;
-  }
-  void release() {
-    if (p) (void)hipHostFree(p);
-    p = nullptr, n = 0;
-  }
-};
-
-using rtxb::round_down;
-using rtxb::round_up;
-
+thread_local std::string g_err;  // rtx_last_error()'s message (fail, rtx_host.h, sets it through rtx_internal_set_error)
 }  // namespace
 
 // statistics, queue counts, then the slot counter block (8 region counters 128 B apart, [128 + 4]
@@ -170,133 +105,6 @@ static double host_us() {
   return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 static thread_local double g_t_launch = 0, g_t_sync0 = 0, g_t_sync1 = 0;
-struct AdaptWs {
-  // lst / kl / ol: the phases' pixel lists (ping-pong: sub-pixel, samples, first slot per entry);
-  // knext: the next batch per entry of the phase just traced; pk: their packed prefix sums
-  // rv: each pixel's predicted convergence count at its last record (k_adapt_plan's pooling)
-  DevBuf lbuf, smap, lst[2], kl[2], ol[2], knext, pk, rv, scan_tmp, ctr;  // ctr: 8 region slot counters (128 B apart), then u64 slot count, pixel count, slot map address, ..., [132] segment buffer, then the spread pixel counts (kSpreadBase)
-  DevBuf segs;                                  // counting renders: each slot's path segments (u16)
-  HostBuf total_h;                              // pinned copy of the next phase's slot count
-  hipEvent_t ev = nullptr;                      // total_h written
-  void release() {
-    for (DevBuf* b : {&lbuf, &smap, &lst[0], &lst[1], &kl[0], &kl[1], &ol[0], &ol[1], &knext, &pk, &rv, &scan_tmp, &ctr,
-                      &segs})
-      b->release();
-    total_h.release();
-    if (ev) (void)hipEventDestroy(ev);
-    ev = nullptr;
-  }
-};
-
-// A film (rtx_film_*): its own pixel state on its scene's device; everything else a render needs
-// (radiance slots, queues, counters, the adaptive workspace) stays the scene's scratch.
-struct rtx_film {
-  rtx_scene* sc = nullptr;  // nullptr once the scene was destroyed (the film's memory went with it)
-  int device = 0;
-  rtx_camera cam{};
-  rtx_render_params prm{};  // spp unused: every rtx_film_render names its budget
-  PixelMap map{};
-  int64_t npix = 0;
-  int32_t done = 0;         // samples done: the film equals a one-shot render at spp = done
-  int64_t epoch = 0;        // the scene's epoch the film was created or last reset at (rtx_film_reset)
-  DevBuf sum, mean, m2, samples, conv;  // mean / m2: adaptive films only
-  mutable DevBuf stage;     // save / load: the blob's body on the device
-  // rtx_film_denoise*: the packed guide and albedo of the film's pixels (float4 each), made on
-  // first use; not part of the saved state
-  DevBuf dn_guide, dn_alb;
-  bool aov_ready = false;
-  PixelSoA px() const {
-    return PixelSoA{sum.as<double>(), mean.as<double>(), m2.as<double>(), samples.as<int32_t>(), conv.as<uint8_t>()};
-  }
-  void release() {
-    for (DevBuf* b : {&sum, &mean, &m2, &samples, &conv, &stage, &dn_guide, &dn_alb}) b->release();
-    aov_ready = false;
-  }
-};
-
-struct rtx_scene {
-  int device = 0;
-  std::vector<rtx_film*> films;  // live films of this scene (rtx_film_create / rtx_film_destroy)
-  hipStream_t stream = nullptr;
-  int cus = 0;
-  DevBuf nodes, prims, mats, texs, images, fnodes, tri_n;
-  // kept for rtx_scene_update_* (DESIGN.md §4c), scenes with nodes: each primitive's reference
-  // box (6 doubles, rtx_prim_bounds) and conservative fast box (6 floats, prim_box rounded
-  // outward), and both trees' node indices grouped by height (a node without child nodes has
-  // height 0); *_lvl: where each height starts in its index array, and the end
-  DevBuf ref_box, fast_box, node_order, f4_order, upd_stage;
-  std::vector<int64_t> node_lvl, f4_lvl;
-  HostBuf upd_host;            // rtx_scene_update_prims: pinned staging of the caller's records
-  std::vector<int8_t> kinds;   // each primitive's kind (an update may not change it)
-  int32_t n_materials = 0;
-  int64_t epoch = 0;           // updates applied so far
-  DevBuf segs1;  // counting adaptive renders: the first phase's per-slot path segments (u16)
-  std::vector<DevBuf> texels;
-  DScene S{};
-  int stack_parity = 32, stack_fast = 32;
-  int fast_need = 0;     // exact worst-case stack depth of the lean BVH4 walk (build_fast4)
-  size_t n_f4 = 0;       // F4Node count of the fast tree
-  bool fast_ok = false;  // RTX_PREC_FAST available (BVH with an internal root)
-  int park = -1;         // persistent fast schedule: -1 not yet timed, 0 plain kernel, 1 PARK kernel
-  DevBuf calib_rgb;      // output of the schedule-timing renders
-  int64_t n_nodes = 0;
-  // render workspace (grow-only)
-  DevBuf px_sum, px_mean, px_m2, px_samples, px_conv, lbuf, queue[2], counters, out_rgb, out_spp, rays, hits;
-  DevBuf p3_scratch, p3_body;  // device P3 encoding (rtx_p3.h)
-  DevBuf occ;                  // rtx_occluded: the rays' bytes (the rays themselves stage through `rays`)
-  // rtx_radiance: the slot scratch (radiance and segments per slot, the carry of a ray summed
-  // across chunks), and the host entry point's staging (pinned on the host; ids, output and
-  // segment totals on the device, the rays through `rays`)
-  DevBuf rad_L, rad_segs, rad_carry, rad_ids, rad_out, rad_oseg;
-  HostBuf rad_host;
-  // rtx_direct (rtx_direct.h): the emitters' primitive indices, fixed at create (kept on the host
-  // too), and their cumulative areas, rebuilt on the device after every update; none: no buffers
-  std::vector<uint32_t> emit_idx;
-  DevBuf emit_prim, emit_cum;
-  DevBuf patch_q;              // adaptive early output: the pixels still sampling when it went
-  // AOVs and the denoiser (rtx_denoise.h): the f64 AOVs of rtx_aov / a film's first denoise, the
-  // host entry points' staged inputs, an adaptive film's variance, and the filter's f32 working
-  // set: colour + variance ping-pong, guide, albedo
-  DevBuf aov_f64, dn_in, dn_var, dn_work[2], dn_guide, dn_alb;
-  HostBuf stage_rgb, stage_spp;  // rtx_render_multi: pinned D2H staging of this device's stripes
-  HostBuf counters_h;            // timed renders: pinned copy of the statistics counters (read after the end event)
-  // ev[0] / ev[1]: a timed render's start and end (rtx_stats.kernel_ms), ev[2] / ev[3]: the
-  // adaptive debug timing, ev[4]: the frame and its output copy done (the host's wait)
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  std::vector<hipEvent_t> evpool;
-  // banded output copies (BandSink): a copy stream and its ordering events
-  hipStream_t copy_stream = nullptr;
-  std::vector<hipEvent_t> band_ev;
-  AdaptWs aw;  // adaptive phases' workspace
-  double slot_mem = -1.0;  // bytes the slot buffers may take (slot_target; -1: not yet queried)
-  ~rtx_scene() {
-    (void)hipSetDevice(device);
-    if (stream) (void)hipStreamSynchronize(stream);
-    // films outlive their scene as empty shells: their device memory goes here, and every call
-    // on them but rtx_film_destroy fails from now on
-    for (rtx_film* f : films) f->release(), f->sc = nullptr;
-    aw.release();
-    for (auto e : evpool) (void)hipEventDestroy(e);
-    for (auto e : band_ev) (void)hipEventDestroy(e);
-    if (copy_stream) (void)hipStreamDestroy(copy_stream);
-    (void)hipSetDevice(device);
-    for (DevBuf* b : {&ref_box, &fast_box, &node_order, &f4_order, &upd_stage}) b->release();
-    upd_host.release();
-    for (DevBuf* b : {&nodes, &prims, &mats, &texs, &images, &fnodes, &tri_n, &px_sum, &px_mean, &px_m2, &px_samples,
-                      &px_conv, &lbuf, &queue[0], &queue[1], &counters, &out_rgb, &out_spp, &rays, &hits, &p3_scratch,
-                      &p3_body, &calib_rgb, &patch_q, &aov_f64, &dn_in, &dn_var, &dn_work[0], &dn_work[1], &dn_guide,
-                      &dn_alb, &occ, &rad_L, &rad_segs, &rad_carry, &rad_ids, &rad_out, &rad_oseg,
-                      &emit_prim, &emit_cum})
-      b->release();
-    rad_host.release();
-    for (auto& t : texels) t.release();
-    stage_rgb.release(), stage_spp.release();
-    for (auto& e : ev)
-      if (e) (void)hipEventDestroy(e);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-};
-
 namespace {
 
 // Tree depth of the reference-layout BVH (pre-order, left = idx+1).
@@ -664,14 +472,6 @@ void plan_fast_tree(const rtx_scene_desc* d, FastPlan& p) {
   }
 }
 
-template <class T>
-int upload(DevBuf& b, const T* src, size_t n, hipStream_t s) {
-  int rc = b.reserve(std::max<size_t>(n * sizeof(T), 16));
-  if (rc) return rc;
-  if (n) HIPC(hipMemcpyAsync(b.p, src, n * sizeof(T), hipMemcpyHostToDevice, s));
-  return RTX_OK;
-}
-
 // Node indices sorted by height (stable), and where each height starts: lvl[k] .. lvl[k + 1] are
 // the nodes of height k in `order`.
 void group_by_height(const std::vector<int>& h, std::vector<uint32_t>& order, std::vector<int64_t>& lvl) {
@@ -685,226 +485,6 @@ void group_by_height(const std::vector<int>& h, std::vector<uint32_t>& order, st
   for (size_t i = 0; i < h.size(); i++) order[(size_t)at[h[i]]++] = (uint32_t)i;
 }
 
-int64_t subset_pixels(const rtx_camera* cam, const rtx_render_params* p, PixelMap& m, std::string& err) {
-  m.W = cam->image_width, m.H = cam->image_height;
-  if (m.W <= 0 || m.H <= 0) {
-    err = "camera not initialised (image size <= 0)";
-    return -1;
-  }
-  if ((int64_t)m.W * m.H > 0x7FFFFFFFll) {  // pixel indices are 32-bit on the device
-    err = "image larger than 2^31 pixels";
-    return -1;
-  }
-  if (p->stripe_rows > 0) {
-    if (p->stripe_count <= 0 || p->stripe_index < 0 || p->stripe_index >= p->stripe_count) {
-      err = "bad stripe_index/stripe_count";
-      return -1;
-    }
-    m.stripes = 1, m.srows = p->stripe_rows, m.sidx = p->stripe_index, m.scount = p->stripe_count;
-    int64_t rows = 0;
-    for (int y = 0; y < m.H; y++)
-      if ((y / m.srows) % m.scount == m.sidx) rows++;
-    m.x0 = m.y0 = 0, m.w = m.W, m.h = (int)rows;
-    set_map_div(m);
-    return rows * (int64_t)m.W;
-  }
-  m.stripes = 0;
-  m.x0 = p->x0, m.y0 = p->y0, m.w = p->w, m.h = p->h;
-  if (m.w == 0 && m.h == 0) m.x0 = 0, m.y0 = 0, m.w = m.W, m.h = m.H;
-  if (m.x0 < 0 || m.y0 < 0 || m.w < 0 || m.h < 0 || m.x0 + m.w > m.W || m.y0 + m.h > m.H) {
-    err = "tile outside the image";
-    return -1;
-  }
-  m.srows = 1, m.sidx = 0, m.scount = 1;
-  set_map_div(m);
-  return (int64_t)m.w * m.h;
-}
-
-template <int STACK, bool FAST>
-int launch_intersect(rtx_scene* sc, const rtx_ray* d_rays, int64_t n, rtx_hit* d_hits, double tmin, double tmax,
-                     hipStream_t s) {
-  const int64_t blocks = (n + kBlock - 1) / kBlock;
-  hipLaunchKernelGGL((k_intersect<STACK, FAST>), dim3((unsigned)blocks), dim3(kBlock),
-                     stack_lds_bytes(STACK), s, sc->S, d_rays, n, d_hits, tmin, tmax);
-  HIPC(hipGetLastError());
-  return RTX_OK;
-}
-
-template <int STACK, bool FAST>
-int launch_aov(rtx_scene* sc, const rtx_camera* cam, const PixelMap& map, int64_t npix, double* d_albedo,
-               double* d_normal, double* d_depth, hipStream_t s) {
-  hipLaunchKernelGGL((k_aov<STACK, FAST>), dim3((unsigned)((npix + kBlock - 1) / kBlock)), dim3(kBlock),
-                     stack_lds_bytes(STACK), s, sc->S, *cam, map, npix, (double)RTX_SEAM_TMIN, d_albedo, d_normal,
-                     d_depth);
-  HIPC(hipGetLastError());
-  return RTX_OK;
-}
-// k_aov over a pixel map, with the walk rtx_intersect_device picks for `precision`
-int aov_on(rtx_scene* sc, const rtx_camera* cam, const PixelMap& map, int64_t npix, int32_t precision, double* d_albedo,
-           double* d_normal, double* d_depth, hipStream_t s) {
-  if (npix == 0) return RTX_OK;
-  const bool fast = precision == RTX_PREC_FAST && sc->fast_ok;
-  const int st = fast ? sc->stack_fast : sc->stack_parity;
-  if (fast) return st == 32 ? launch_aov<32, true>(sc, cam, map, npix, d_albedo, d_normal, d_depth, s)
-                            : launch_aov<64, true>(sc, cam, map, npix, d_albedo, d_normal, d_depth, s);
-  return st == 32 ? launch_aov<32, false>(sc, cam, map, npix, d_albedo, d_normal, d_depth, s)
-                  : launch_aov<64, false>(sc, cam, map, npix, d_albedo, d_normal, d_depth, s);
-}
-// ---- occlusion queries and the AO pass (rtx_occlusion.h): the walk is picked as in
-// rtx_intersect_device (fast only with a fast tree, the scene's stack size) ----
-template <int STACK, bool FAST>
-int launch_occluded(rtx_scene* sc, const rtx_ray* d_rays, int64_t n, uint8_t* d_out, double tmin, double tmax,
-                    hipStream_t s) {
-  hipLaunchKernelGGL((k_occluded<STACK, FAST>), dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock),
-                     stack_lds_bytes(STACK), s, sc->S, d_rays, n, d_out, tmin, tmax);
-  HIPC(hipGetLastError());
-  return RTX_OK;
-}
-// rays == nullptr: k_ao into d_out; else k_ao_rays (the test hook's sample rays)
-template <int STACK, bool FAST>
-int launch_ao(rtx_scene* sc, const rtx_camera* cam, const PixelMap& map, int64_t npix, const rtx_ao_params* ao,
-              double* d_out, rtx_ray* d_rays, hipStream_t s) {
-  const dim3 grid((unsigned)((npix + kBlock - 1) / kBlock));
-  if (d_rays)
-    hipLaunchKernelGGL((k_ao_rays<STACK, FAST>), grid, dim3(kBlock), stack_lds_bytes(STACK), s, sc->S, *cam, map, npix,
-                       ao->seed, ao->samples, d_rays);
-  else
-    hipLaunchKernelGGL((k_ao<STACK, FAST>), grid, dim3(kBlock), stack_lds_bytes(STACK), s, sc->S, *cam, map, npix,
-                       ao->seed, ao->samples, ao->radius, d_out);
-  HIPC(hipGetLastError());
-  return RTX_OK;
-}
-int ao_on(rtx_scene* sc, const rtx_camera* cam, const PixelMap& map, int64_t npix, int32_t precision,
-          const rtx_ao_params* ao, double* d_out, rtx_ray* d_rays, hipStream_t s) {
-  if (npix == 0) return RTX_OK;
-  const bool fast = precision == RTX_PREC_FAST && sc->fast_ok;
-  const int st = fast ? sc->stack_fast : sc->stack_parity;
-  if (fast) return st == 32 ? launch_ao<32, true>(sc, cam, map, npix, ao, d_out, d_rays, s)
-                            : launch_ao<64, true>(sc, cam, map, npix, ao, d_out, d_rays, s);
-  return st == 32 ? launch_ao<32, false>(sc, cam, map, npix, ao, d_out, d_rays, s)
-                  : launch_ao<64, false>(sc, cam, map, npix, ao, d_out, d_rays, s);
-}
-// the checks rtx_ao, rtx_ao_device and rtx_internal_ao_rays share; *npix: pixels of the subset
-int ao_check(const rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, const rtx_ao_params* ao,
-             PixelMap& map, int64_t* npix) {
-  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
-  if (!cam || !prm || !ao) return fail(RTX_ERR_INVALID, "NULL argument");
-  if (ao->samples < 1 || ao->samples > 1024) return fail(RTX_ERR_INVALID, "ao: samples outside 1..1024");
-  if (!(ao->radius > 0)) return fail(RTX_ERR_INVALID, "ao: radius must be positive");
-  std::string err;
-  *npix = subset_pixels(cam, prm, map, err);
-  if (*npix < 0) return fail(RTX_ERR_INVALID, err);
-  return RTX_OK;
-}
-// ---- radiance queries (rtx_radiance.h): the walk is picked as in rtx_intersect_device ----
-// the slot cap of the calls that follow (rtx_internal_radiance_chunk; 0: kRadianceSlots)
-std::atomic<int64_t> g_radiance_chunk{0};
-template <int STACK, bool FAST>
-int launch_radiance(rtx_scene* sc, const RadianceChunk& A, hipStream_t s) {
-  hipLaunchKernelGGL((k_radiance<STACK, FAST>), dim3((A.slots + kBlock - 1) / kBlock), dim3(kBlock),
-                     stack_lds_bytes(STACK), s, sc->S, A);
-  HIPC(hipGetLastError());
-  return RTX_OK;
-}
-// the same launch of k_irradiance (rtx_irradiance.h): A.rays are surfels
-template <int STACK, bool FAST>
-int launch_irradiance(rtx_scene* sc, const RadianceChunk& A, hipStream_t s) {
-  hipLaunchKernelGGL((k_irradiance<STACK, FAST>), dim3((A.slots + kBlock - 1) / kBlock), dim3(kBlock),
-                     stack_lds_bytes(STACK), s, sc->S, A);
-  HIPC(hipGetLastError());
-  return RTX_OK;
-}
-// ---- direct-lighting queries (rtx_direct.h) ----
-EmitterTable emitter_table(const rtx_scene* sc) {
-  return EmitterTable{sc->emit_prim.as<uint32_t>(), sc->emit_cum.as<double>(), (int64_t)sc->emit_idx.size()};
-}
-// The emitters' areas and their running sum from the live primitives, on `s`: at create, and at
-// the end of every in-place update.  A scene without emitters launches nothing.
-int emitters_rebuild(rtx_scene* sc, hipStream_t s) {
-  const EmitterTable E = emitter_table(sc);
-  if (E.n <= 0) return RTX_OK;
-  hipLaunchKernelGGL(k_emitter_area, dim3((unsigned)((E.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
-                     sc->prims.as<rtx_prim>(), E);
-  HIPC(hipGetLastError());
-  hipLaunchKernelGGL(k_emitter_scan, dim3(1), dim3(kBlock), 0, s, E);
-  HIPC(hipGetLastError());
-  return RTX_OK;
-}
-// launch_radiance's launch of k_direct: A.rays are surfels
-template <int STACK, bool FAST>
-int launch_direct(rtx_scene* sc, const RadianceChunk& A, hipStream_t s) {
-  hipLaunchKernelGGL((k_direct<STACK, FAST>), dim3((A.slots + kBlock - 1) / kBlock), dim3(kBlock),
-                     stack_lds_bytes(STACK), s, sc->S, emitter_table(sc), A);
-  HIPC(hipGetLastError());
-  return RTX_OK;
-}
-// what a chunk's slots hold (radiance_on): a path from a caller's ray, a path from a surfel's
-// hemisphere sample, or a surfel's emitter sample
-enum SlotKind { kSlotRadiance = 0, kSlotIrradiance = 1, kSlotDirect = 2 };
-// the checks rtx_radiance*, rtx_irradiance*, rtx_direct* and their test hooks share, in the documented order
-int radiance_check(const rtx_scene* sc, const rtx_radiance_params* prm, const void* rays, const void* out) {
-  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
-  if (!prm) return fail(RTX_ERR_INVALID, "NULL argument");
-  if (!rays || !out) return fail(RTX_ERR_INVALID, "NULL buffer");
-  if (prm->spp < 1) return fail(RTX_ERR_INVALID, "radiance: spp must be at least 1");
-  if (prm->first_sample < 0 || prm->first_sample > 0x7FFFFFFF - prm->spp)
-    return fail(RTX_ERR_INVALID, "radiance: first_sample must be >= 0 and first_sample + spp fit int32");
-  if (prm->max_depth < 0) return fail(RTX_ERR_INVALID, "negative max_depth");
-  if (prm->precision != RTX_PREC_PARITY && prm->precision != RTX_PREC_FAST)
-    return fail(RTX_ERR_INVALID, "radiance: bad precision");
-  return RTX_OK;
-}
-// n > 0 rays on device buffers, in chunks of at most `cap` slots (ray x sample): whole rays per
-// chunk, or, when one ray's samples exceed the cap, one ray at a time in runs of `cap` samples
-// whose partial sum k_radiance_sum carries.  id_base: the pixel key of d_rays[0] when d_ids is
-// null (the host entry point's batches).  what: for kSlotIrradiance and kSlotDirect d_rays are
-// surfels and the slots are k_irradiance's (rtx_irradiance*) or k_direct's (rtx_direct*: a
-// slot's "segments" are its visibility, 0 or 1); the chunking, the scratch and the sum are the same.
-int radiance_on(rtx_scene* sc, const rtx_ray* d_rays, const uint32_t* d_ids, uint64_t id_base, int64_t n,
-                const rtx_radiance_params* prm, double* d_out, uint32_t* d_segs, hipStream_t s,
-                SlotKind what = kSlotRadiance) {
-  const int64_t tuned = g_radiance_chunk.load();
-  const int64_t cap = std::min<int64_t>(tuned > 0 ? tuned : kRadianceSlots, kRadianceSlotsMax);
-  const int64_t spp = prm->spp;
-  const int64_t rays_per = std::max<int64_t>(1, cap / spp);  // rays per chunk
-  const int64_t k_per = std::min<int64_t>(spp, cap);         // samples of a ray per chunk
-  const int64_t most = std::min<int64_t>(n, rays_per) * k_per;  // slots of the largest chunk (<= cap)
-  int rc;
-  if ((rc = sc->rad_L.reserve((size_t)most * 3 * sizeof(double)))) return rc;
-  if ((rc = sc->rad_segs.reserve((size_t)most * sizeof(uint32_t)))) return rc;
-  if (k_per < spp) {  // (one ray per chunk)
-    if ((rc = sc->rad_carry.reserve(4 * sizeof(double)))) return rc;
-  }
-  const bool fast = prm->precision == RTX_PREC_FAST && sc->fast_ok;
-  const int st = fast ? sc->stack_fast : sc->stack_parity;
-  double* const carry = k_per < spp ? sc->rad_carry.as<double>() : nullptr;
-  for (int64_t r0 = 0; r0 < n; r0 += rays_per) {
-    const int64_t nr = std::min<int64_t>(rays_per, n - r0);
-    for (int64_t k0 = 0; k0 < spp; k0 += k_per) {
-      const int64_t K = std::min<int64_t>(k_per, spp - k0);
-      RadianceChunk A;
-      A.rays = d_rays, A.ids = d_ids, A.ray0 = r0, A.id_base = id_base;
-      A.slots = (uint32_t)(nr * K), A.K = (uint32_t)K;
-      A.s0 = (int32_t)(prm->first_sample + k0), A.max_depth = prm->max_depth, A.seed = prm->seed;
-      A.L = sc->rad_L.as<double>(), A.segs = sc->rad_segs.as<uint32_t>();
-      if (what == kSlotDirect) {
-        if (fast) rc = st == 32 ? launch_direct<32, true>(sc, A, s) : launch_direct<64, true>(sc, A, s);
-        else rc = st == 32 ? launch_direct<32, false>(sc, A, s) : launch_direct<64, false>(sc, A, s);
-      } else if (what == kSlotIrradiance) {
-        if (fast) rc = st == 32 ? launch_irradiance<32, true>(sc, A, s) : launch_irradiance<64, true>(sc, A, s);
-        else rc = st == 32 ? launch_irradiance<32, false>(sc, A, s) : launch_irradiance<64, false>(sc, A, s);
-      } else if (fast) rc = st == 32 ? launch_radiance<32, true>(sc, A, s) : launch_radiance<64, true>(sc, A, s);
-      else rc = st == 32 ? launch_radiance<32, false>(sc, A, s) : launch_radiance<64, false>(sc, A, s);
-      if (rc) return rc;
-      hipLaunchKernelGGL(k_radiance_sum, dim3((unsigned)((nr + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
-                         sc->rad_L.as<double>(), sc->rad_segs.as<uint32_t>(), nr, (uint32_t)K, k0 == 0 ? 1 : 0,
-                         k0 + K == spp ? 1 : 0, prm->spp, carry, carry ? (uint32_t*)(carry + 3) : nullptr,
-                         d_out + 3 * r0, d_segs ? d_segs + r0 : nullptr);
-      HIPC(hipGetLastError());
-    }
-  }
-  return RTX_OK;
-}
 int persistent_grid(rtx_scene* sc, const void* fn, size_t lds) {
   int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kBlock, lds) != hipSuccess || per_cu <= 0)
@@ -994,13 +574,10 @@ int run_persistent(const Launch& L, const RenderArgs& A, unsigned long long* nex
 }
 
 // template dispatch helpers
-template <bool FAST, bool COUNT>
-int extend_s(const Launch& L, const RenderArgs& A, const PathQueue& q, const unsigned* c, int64_t n) {
-  return L.stack == 32 ? run_extend<32, FAST, COUNT>(L, A, q, c, n) : run_extend<64, FAST, COUNT>(L, A, q, c, n);
-}
 int extend(const Launch& L, const RenderArgs& A, const PathQueue& q, const unsigned* c, int64_t n) {
-  if (L.fast) return L.count ? extend_s<true, true>(L, A, q, c, n) : extend_s<true, false>(L, A, q, c, n);
-  return L.count ? extend_s<false, true>(L, A, q, c, n) : extend_s<false, false>(L, A, q, c, n);
+  return with_walk(L.stack, L.fast, [&](auto w) {
+    return L.count ? run_extend<w.stack, w.fast, true>(L, A, q, c, n) : run_extend<w.stack, w.fast, false>(L, A, q, c, n);
+  });
 }
 template <bool FAST, bool COUNT, bool SCATTER, int PARK>
 int persist_s(const Launch& L, const RenderArgs& A, unsigned long long* ns) {
@@ -1534,307 +1111,6 @@ int rtx_internal_scene_trees(rtx_scene* sc, void* nodes_out, int64_t nodes_cap, 
   if (f4_out && nf)
     HIPC(hipMemcpyAsync(f4_out, sc->fnodes.p, (size_t)nf * sizeof(F4Node), hipMemcpyDeviceToHost, sc->stream));
   HIPC(hipStreamSynchronize(sc->stream));
-  return RTX_OK;
-}
-
-int rtx_intersect_device(rtx_scene* sc, const rtx_ray* d_rays, size_t n, rtx_hit* d_hits, double tmin, double tmax,
-                         int32_t precision, void* stream) {
-  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
-  if (n == 0) return RTX_OK;
-  if (!d_rays || !d_hits) return fail(RTX_ERR_INVALID, "NULL buffer");
-  HIPC(hipSetDevice(sc->device));
-  hipStream_t s = stream ? (hipStream_t)stream : sc->stream;
-  const bool fast = precision == RTX_PREC_FAST && sc->fast_ok;
-  const int st = fast ? sc->stack_fast : sc->stack_parity;
-  if (fast) return st == 32 ? launch_intersect<32, true>(sc, d_rays, (int64_t)n, d_hits, tmin, tmax, s)
-                            : launch_intersect<64, true>(sc, d_rays, (int64_t)n, d_hits, tmin, tmax, s);
-  return st == 32 ? launch_intersect<32, false>(sc, d_rays, (int64_t)n, d_hits, tmin, tmax, s)
-                  : launch_intersect<64, false>(sc, d_rays, (int64_t)n, d_hits, tmin, tmax, s);
-}
-
-int rtx_intersect(rtx_scene* sc, const rtx_ray* rays, size_t n, rtx_hit* hits, double tmin, double tmax,
-                  int32_t precision) {
-  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
-  if (n == 0) return RTX_OK;
-  if (!rays || !hits) return fail(RTX_ERR_INVALID, "NULL buffer");
-  HIPC(hipSetDevice(sc->device));
-  int rc;
-  if ((rc = sc->rays.reserve(n * sizeof(rtx_ray)))) return rc;
-  if ((rc = sc->hits.reserve(n * sizeof(rtx_hit)))) return rc;
-  HIPC(hipMemcpyAsync(sc->rays.p, rays, n * sizeof(rtx_ray), hipMemcpyHostToDevice, sc->stream));
-  if ((rc = rtx_intersect_device(sc, sc->rays.as<rtx_ray>(), n, sc->hits.as<rtx_hit>(), tmin, tmax, precision,
-                                 sc->stream)))
-    return rc;
-  HIPC(hipMemcpyAsync(hits, sc->hits.p, n * sizeof(rtx_hit), hipMemcpyDeviceToHost, sc->stream));
-  HIPC(hipStreamSynchronize(sc->stream));
-  return RTX_OK;
-}
-
-int rtx_occluded_device(rtx_scene* sc, const rtx_ray* d_rays, size_t n, uint8_t* d_out, double tmin, double tmax,
-                        int32_t precision, void* stream) {
-  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
-  if (!(tmin < tmax)) return fail(RTX_ERR_INVALID, "occluded: tmin must be below tmax");
-  if (n == 0) return RTX_OK;
-  if (!d_rays || !d_out) return fail(RTX_ERR_INVALID, "NULL buffer");
-  HIPC(hipSetDevice(sc->device));
-  hipStream_t s = stream ? (hipStream_t)stream : sc->stream;
-  const bool fast = precision == RTX_PREC_FAST && sc->fast_ok;
-  const int st = fast ? sc->stack_fast : sc->stack_parity;
-  if (fast) return st == 32 ? launch_occluded<32, true>(sc, d_rays, (int64_t)n, d_out, tmin, tmax, s)
-                            : launch_occluded<64, true>(sc, d_rays, (int64_t)n, d_out, tmin, tmax, s);
-  return st == 32 ? launch_occluded<32, false>(sc, d_rays, (int64_t)n, d_out, tmin, tmax, s)
-                  : launch_occluded<64, false>(sc, d_rays, (int64_t)n, d_out, tmin, tmax, s);
-}
-
-int rtx_occluded(rtx_scene* sc, const rtx_ray* rays, size_t n, uint8_t* out, double tmin, double tmax,
-                 int32_t precision) {
-  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
-  if (!(tmin < tmax)) return fail(RTX_ERR_INVALID, "occluded: tmin must be below tmax");
-  if (n == 0) return RTX_OK;
-  if (!rays || !out) return fail(RTX_ERR_INVALID, "NULL buffer");
-  HIPC(hipSetDevice(sc->device));
-  int rc;
-  if ((rc = sc->rays.reserve(n * sizeof(rtx_ray)))) return rc;
-  if ((rc = sc->occ.reserve(n))) return rc;
-  HIPC(hipMemcpyAsync(sc->rays.p, rays, n * sizeof(rtx_ray), hipMemcpyHostToDevice, sc->stream));
-  if ((rc = rtx_occluded_device(sc, sc->rays.as<rtx_ray>(), n, sc->occ.as<uint8_t>(), tmin, tmax, precision, sc->stream)))
-    return rc;
-  HIPC(hipMemcpyAsync(out, sc->occ.p, n, hipMemcpyDeviceToHost, sc->stream));
-  HIPC(hipStreamSynchronize(sc->stream));
-  return RTX_OK;
-}
-
-int rtx_ao_device(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, const rtx_ao_params* ao,
-                  double* d_out, void* stream) {
-  PixelMap map;
-  int64_t npix;
-  int rc;
-  if ((rc = ao_check(sc, cam, prm, ao, map, &npix))) return rc;
-  if (npix == 0) return RTX_OK;
-  if (!d_out) return fail(RTX_ERR_INVALID, "NULL buffer");
-  HIPC(hipSetDevice(sc->device));
-  return ao_on(sc, cam, map, npix, prm->precision, ao, d_out, nullptr, stream ? (hipStream_t)stream : sc->stream);
-}
-
-int rtx_ao(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, const rtx_ao_params* ao, double* out) {
-  PixelMap map;
-  int64_t npix;
-  int rc;
-  if ((rc = ao_check(sc, cam, prm, ao, map, &npix))) return rc;
-  if (npix == 0) return RTX_OK;
-  if (!out) return fail(RTX_ERR_INVALID, "NULL buffer");
-  HIPC(hipSetDevice(sc->device));
-  if ((rc = sc->aov_f64.reserve((size_t)npix * sizeof(double)))) return rc;  // (the AOV staging: one double per pixel)
-  if ((rc = ao_on(sc, cam, map, npix, prm->precision, ao, sc->aov_f64.as<double>(), nullptr, sc->stream))) return rc;
-  HIPC(hipMemcpyAsync(out, sc->aov_f64.p, (size_t)npix * sizeof(double), hipMemcpyDeviceToHost, sc->stream));
-  HIPC(hipStreamSynchronize(sc->stream));
-  return RTX_OK;
-}
-
-// Test hook (not in rtx.h): the sample rays of rtx_ao for the same arguments, npix * samples of
-// them, pixel major, made by the device function k_ao calls (ao_direction after ao_first_hit,
-// rtx_occlusion.h) and copied to the host; a pixel that misses has all-zero rays.
-extern "C" int rtx_internal_ao_rays(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm,
-                                    const rtx_ao_params* ao, rtx_ray* out) {
-  PixelMap map;
-  int64_t npix;
-  int rc;
-  if ((rc = ao_check(sc, cam, prm, ao, map, &npix))) return rc;
-  if (npix == 0) return RTX_OK;
-  if (!out) return fail(RTX_ERR_INVALID, "NULL buffer");
-  HIPC(hipSetDevice(sc->device));
-  const size_t bytes = (size_t)npix * (size_t)ao->samples * sizeof(rtx_ray);
-  if ((rc = sc->rays.reserve(bytes))) return rc;
-  if ((rc = ao_on(sc, cam, map, npix, prm->precision, ao, nullptr, sc->rays.as<rtx_ray>(), sc->stream))) return rc;
-  HIPC(hipMemcpyAsync(out, sc->rays.p, bytes, hipMemcpyDeviceToHost, sc->stream));
-  HIPC(hipStreamSynchronize(sc->stream));
-  return RTX_OK;
-}
-
-int rtx_radiance_device(rtx_scene* sc, const rtx_ray* d_rays, const uint32_t* d_ids, size_t n,
-                        const rtx_radiance_params* prm, double* d_out_rgb, uint32_t* d_out_segments, void* stream) {
-  int rc;
-  if ((rc = radiance_check(sc, prm, d_rays, d_out_rgb))) return rc;
-  if (n == 0) return RTX_OK;
-  HIPC(hipSetDevice(sc->device));
-  return radiance_on(sc, d_rays, d_ids, 0, (int64_t)n, prm, d_out_rgb, d_out_segments,
-                     stream ? (hipStream_t)stream : sc->stream);
-}
-
-// The host entry point works in batches of kRadianceHostRays rays: the caller's rays and ids are
-// copied into pinned memory, traced, and the results copied back out of it.
-constexpr size_t kRadianceHostRays = (size_t)1 << 20;
-// (shared with rtx_irradiance and rtx_direct, whose rays are surfels)
-static int radiance_host(rtx_scene* sc, const rtx_ray* rays, const uint32_t* ids, size_t n,
-                         const rtx_radiance_params* prm, double* out_rgb, uint32_t* out_segments, SlotKind what) {
-  int rc;
-  if ((rc = radiance_check(sc, prm, rays, out_rgb))) return rc;
-  if (n == 0) return RTX_OK;
-  HIPC(hipSetDevice(sc->device));
-  const size_t m = std::min(n, kRadianceHostRays);
-  // pinned: rays | rgb | ids | segments (8-byte items first)
-  const size_t off_rgb = m * sizeof(rtx_ray), off_ids = off_rgb + m * 3 * sizeof(double),
-               off_seg = off_ids + m * sizeof(uint32_t);
-  if ((rc = sc->rad_host.reserve(off_seg + m * sizeof(uint32_t)))) return rc;
-  if ((rc = sc->rays.reserve(m * sizeof(rtx_ray)))) return rc;
-  if ((rc = sc->rad_out.reserve(m * 3 * sizeof(double)))) return rc;
-  if ((rc = sc->rad_oseg.reserve(m * sizeof(uint32_t)))) return rc;
-  if (ids && (rc = sc->rad_ids.reserve(m * sizeof(uint32_t)))) return rc;
-  char* const pin = (char*)sc->rad_host.p;
-  for (size_t b0 = 0; b0 < n; b0 += m) {
-    const size_t nb = std::min(m, n - b0);
-    std::memcpy(pin, rays + b0, nb * sizeof(rtx_ray));
-    HIPC(hipMemcpyAsync(sc->rays.p, pin, nb * sizeof(rtx_ray), hipMemcpyHostToDevice, sc->stream));
-    if (ids) {
-      std::memcpy(pin + off_ids, ids + b0, nb * sizeof(uint32_t));
-      HIPC(hipMemcpyAsync(sc->rad_ids.p, pin + off_ids, nb * sizeof(uint32_t), hipMemcpyHostToDevice, sc->stream));
-    }
-    if ((rc = radiance_on(sc, sc->rays.as<rtx_ray>(), ids ? sc->rad_ids.as<uint32_t>() : nullptr, (uint64_t)b0,
-                          (int64_t)nb, prm, sc->rad_out.as<double>(), sc->rad_oseg.as<uint32_t>(), sc->stream, what)))
-      return rc;
-    HIPC(hipMemcpyAsync(pin + off_rgb, sc->rad_out.p, nb * 3 * sizeof(double), hipMemcpyDeviceToHost, sc->stream));
-    if (out_segments)
-      HIPC(hipMemcpyAsync(pin + off_seg, sc->rad_oseg.p, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, sc->stream));
-    HIPC(hipStreamSynchronize(sc->stream));
-    std::memcpy(out_rgb + 3 * b0, pin + off_rgb, nb * 3 * sizeof(double));
-    if (out_segments) std::memcpy(out_segments + b0, pin + off_seg, nb * sizeof(uint32_t));
-  }
-  return RTX_OK;
-}
-int rtx_radiance(rtx_scene* sc, const rtx_ray* rays, const uint32_t* ids, size_t n, const rtx_radiance_params* prm,
-                 double* out_rgb, uint32_t* out_segments) {
-  return radiance_host(sc, rays, ids, n, prm, out_rgb, out_segments, kSlotRadiance);
-}
-
-// ---- irradiance queries (rtx_irradiance.h): rtx_radiance's checks, chunks and staging ----
-int rtx_irradiance_device(rtx_scene* sc, const rtx_ray* d_surfels, const uint32_t* d_ids, size_t n,
-                          const rtx_radiance_params* prm, double* d_out_rgb, uint32_t* d_out_segments, void* stream) {
-  int rc;
-  if ((rc = radiance_check(sc, prm, d_surfels, d_out_rgb))) return rc;
-  if (n == 0) return RTX_OK;
-  HIPC(hipSetDevice(sc->device));
-  return radiance_on(sc, d_surfels, d_ids, 0, (int64_t)n, prm, d_out_rgb, d_out_segments,
-                     stream ? (hipStream_t)stream : sc->stream, kSlotIrradiance);
-}
-
-int rtx_irradiance(rtx_scene* sc, const rtx_ray* surfels, const uint32_t* ids, size_t n,
-                   const rtx_radiance_params* prm, double* out_rgb, uint32_t* out_segments) {
-  return radiance_host(sc, surfels, ids, n, prm, out_rgb, out_segments, kSlotIrradiance);
-}
-
-// Test hook (not in rtx.h): the depth-0 segments rtx_irradiance traces for the same arguments
-// (seed, first_sample and spp of prm are read; the rest is checked as there), n x spp x 6
-// doubles (origin, direction), surfel major, made by the device function k_irradiance calls
-// (irradiance_ray, rtx_irradiance.h); all zero for a surfel with a degenerate normal.  Host
-// buffers.
-extern "C" int rtx_internal_irradiance_rays(rtx_scene* sc, const rtx_ray* surfels, const uint32_t* ids, size_t n,
-                                            const rtx_radiance_params* prm, double* out) {
-  int rc;
-  if ((rc = radiance_check(sc, prm, surfels, out))) return rc;
-  if (n == 0) return RTX_OK;
-  if (n > (size_t)kRadianceSlotsMax || (int64_t)n * prm->spp > kRadianceSlotsMax)
-    return fail(RTX_ERR_INVALID, "irradiance rays: too many rays for one call");
-  HIPC(hipSetDevice(sc->device));
-  const uint32_t nslots = (uint32_t)(n * (size_t)prm->spp);
-  const size_t bytes = (size_t)nslots * 6 * sizeof(double);
-  if ((rc = sc->rays.reserve(n * sizeof(rtx_ray)))) return rc;
-  if ((rc = sc->rad_L.reserve(bytes))) return rc;
-  if (ids && (rc = sc->rad_ids.reserve(n * sizeof(uint32_t)))) return rc;
-  HIPC(hipMemcpyAsync(sc->rays.p, surfels, n * sizeof(rtx_ray), hipMemcpyHostToDevice, sc->stream));
-  if (ids) HIPC(hipMemcpyAsync(sc->rad_ids.p, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, sc->stream));
-  hipLaunchKernelGGL(k_irradiance_rays, dim3((nslots + kBlock - 1) / kBlock), dim3(kBlock), 0, sc->stream,
-                     sc->rays.as<rtx_ray>(), ids ? sc->rad_ids.as<uint32_t>() : nullptr, nslots, (uint32_t)prm->spp,
-                     prm->seed, prm->first_sample, sc->rad_L.as<double>());
-  HIPC(hipGetLastError());
-  HIPC(hipMemcpyAsync(out, sc->rad_L.p, bytes, hipMemcpyDeviceToHost, sc->stream));
-  HIPC(hipStreamSynchronize(sc->stream));
-  return RTX_OK;
-}
-
-// ---- direct-lighting queries (rtx_direct.h): rtx_radiance's checks, chunks and staging ----
-int rtx_direct_device(rtx_scene* sc, const rtx_ray* d_surfels, const uint32_t* d_ids, size_t n,
-                      const rtx_radiance_params* prm, double* d_out_rgb, uint32_t* d_out_visible, void* stream) {
-  int rc;
-  if ((rc = radiance_check(sc, prm, d_surfels, d_out_rgb))) return rc;
-  if (n == 0) return RTX_OK;
-  HIPC(hipSetDevice(sc->device));
-  return radiance_on(sc, d_surfels, d_ids, 0, (int64_t)n, prm, d_out_rgb, d_out_visible,
-                     stream ? (hipStream_t)stream : sc->stream, kSlotDirect);
-}
-
-int rtx_direct(rtx_scene* sc, const rtx_ray* surfels, const uint32_t* ids, size_t n, const rtx_radiance_params* prm,
-               double* out_rgb, uint32_t* out_visible) {
-  return radiance_host(sc, surfels, ids, n, prm, out_rgb, out_visible, kSlotDirect);
-}
-
-int rtx_scene_emitters(const rtx_scene* sc, int64_t* count, double* area) {
-  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
-  if (!count && !area) return fail(RTX_ERR_INVALID, "NULL argument");
-  const int64_t n = (int64_t)sc->emit_idx.size();
-  if (count) *count = n;
-  if (area) {
-    *area = 0.0;
-    if (n > 0) {
-      HIPC(hipSetDevice(sc->device));
-      HIPC(hipStreamSynchronize(sc->stream));
-      HIPC(hipMemcpy(area, sc->emit_cum.as<double>() + (n - 1), sizeof(double), hipMemcpyDeviceToHost));
-    }
-  }
-  return RTX_OK;
-}
-
-// Test hook (not in rtx.h): the samples rtx_direct draws for the same arguments (seed,
-// first_sample and spp of prm are read; the rest is checked as there), n x spp x 9 doubles
-// (segment origin, y - x, the unshadowed contribution C), surfel major, made by the device
-// function k_direct calls (direct_sample, rtx_direct.h); all zero where nothing is traced.  Host
-// buffers.
-extern "C" int rtx_internal_direct_samples(rtx_scene* sc, const rtx_ray* surfels, const uint32_t* ids, size_t n,
-                                           const rtx_radiance_params* prm, double* out) {
-  int rc;
-  if ((rc = radiance_check(sc, prm, surfels, out))) return rc;
-  if (n == 0) return RTX_OK;
-  if (n > (size_t)kRadianceSlotsMax || (int64_t)n * prm->spp > kRadianceSlotsMax)
-    return fail(RTX_ERR_INVALID, "direct samples: too many samples for one call");
-  HIPC(hipSetDevice(sc->device));
-  const uint32_t nslots = (uint32_t)(n * (size_t)prm->spp);
-  const size_t bytes = (size_t)nslots * 9 * sizeof(double);
-  if ((rc = sc->rays.reserve(n * sizeof(rtx_ray)))) return rc;
-  if ((rc = sc->rad_L.reserve(bytes))) return rc;
-  if (ids && (rc = sc->rad_ids.reserve(n * sizeof(uint32_t)))) return rc;
-  HIPC(hipMemcpyAsync(sc->rays.p, surfels, n * sizeof(rtx_ray), hipMemcpyHostToDevice, sc->stream));
-  if (ids) HIPC(hipMemcpyAsync(sc->rad_ids.p, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, sc->stream));
-  hipLaunchKernelGGL(k_direct_samples, dim3((nslots + kBlock - 1) / kBlock), dim3(kBlock), 0, sc->stream, sc->S,
-                     emitter_table(sc), sc->rays.as<rtx_ray>(), ids ? sc->rad_ids.as<uint32_t>() : nullptr, nslots,
-                     (uint32_t)prm->spp, prm->seed, prm->first_sample, sc->rad_L.as<double>());
-  HIPC(hipGetLastError());
-  HIPC(hipMemcpyAsync(out, sc->rad_L.p, bytes, hipMemcpyDeviceToHost, sc->stream));
-  HIPC(hipStreamSynchronize(sc->stream));
-  return RTX_OK;
-}
-
-// Test hook (not in rtx.h): the live emitter table copied back after everything queued on the
-// scene's stream, at most `cap` entries: each emitter's primitive index (the caller's own order,
-// as rtx_scene_update_prims counts it) and the inclusive cumulative areas.  Either may be NULL.
-extern "C" int rtx_internal_emitters(rtx_scene* sc, int64_t* prims_out, double* cum_out, int64_t cap) {
-  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
-  const int64_t n = std::min<int64_t>(std::max<int64_t>(0, cap), (int64_t)sc->emit_idx.size());
-  if (n == 0) return RTX_OK;
-  if (prims_out)
-    for (int64_t i = 0; i < n; i++) prims_out[i] = (int64_t)sc->emit_idx[(size_t)i];
-  if (cum_out) {
-    HIPC(hipSetDevice(sc->device));
-    HIPC(hipStreamSynchronize(sc->stream));
-    HIPC(hipMemcpy(cum_out, sc->emit_cum.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-  }
-  return RTX_OK;
-}
-
-// Test hook (not in rtx.h): the slot cap of the radiance calls that follow in this process
-// (0 restores kRadianceSlots), so chunk seams are reached at small shapes.  Results never
-// depend on it.
-extern "C" int rtx_internal_radiance_chunk(int64_t slots) {
-  if (slots < 0) return fail(RTX_ERR_INVALID, "radiance chunk: negative slot count");
-  g_radiance_chunk.store(slots);
   return RTX_OK;
 }
 
@@ -2853,42 +2129,6 @@ int denoise_work(rtx_scene* sc, int64_t npix, bool guides) {
 int rtx_denoise_params_default(rtx_denoise_params* out) {
   if (!out) return fail(RTX_ERR_INVALID, "NULL argument");
   *out = kDenoiseDefaults;
-  return RTX_OK;
-}
-
-int rtx_aov_device(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, double* d_albedo,
-                   double* d_normal, double* d_depth, void* stream) {
-  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
-  if (!cam || !prm) return fail(RTX_ERR_INVALID, "NULL argument");
-  PixelMap map;
-  std::string err;
-  const int64_t npix = subset_pixels(cam, prm, map, err);
-  if (npix < 0) return fail(RTX_ERR_INVALID, err);
-  HIPC(hipSetDevice(sc->device));
-  return aov_on(sc, cam, map, npix, prm->precision, d_albedo, d_normal, d_depth, stream ? (hipStream_t)stream : sc->stream);
-}
-
-int rtx_aov(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, double* albedo, double* normal,
-            double* depth) {
-  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
-  if (!cam || !prm) return fail(RTX_ERR_INVALID, "NULL argument");
-  PixelMap map;
-  std::string err;
-  const int64_t npix = subset_pixels(cam, prm, map, err);
-  if (npix < 0) return fail(RTX_ERR_INVALID, err);
-  if (npix == 0) return RTX_OK;
-  HIPC(hipSetDevice(sc->device));
-  int rc;
-  if ((rc = sc->aov_f64.reserve((size_t)npix * 7 * sizeof(double)))) return rc;
-  double* a = sc->aov_f64.as<double>();  // albedo 3 n, normal 3 n, depth n
-  double *n = a + 3 * npix, *d = a + 6 * npix;
-  hipStream_t s = sc->stream;
-  if ((rc = aov_on(sc, cam, map, npix, prm->precision, albedo ? a : nullptr, normal ? n : nullptr, depth ? d : nullptr, s)))
-    return rc;
-  if (albedo) HIPC(hipMemcpyAsync(albedo, a, (size_t)npix * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (normal) HIPC(hipMemcpyAsync(normal, n, (size_t)npix * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (depth) HIPC(hipMemcpyAsync(depth, d, (size_t)npix * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPC(hipStreamSynchronize(s));
   return RTX_OK;
 }
 

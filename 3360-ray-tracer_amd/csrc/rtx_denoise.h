@@ -2,7 +2,7 @@
 // rtx_film_denoise*, include/rtx.h; DESIGN.md §4b "AOVs and the denoiser").
 // Here: the filter's launch interface (its kernels are their own translation unit,
 // rtx_denoise.hip) and, for the translation unit that holds the trace kernels
-// (RTX_DENOISE_AOV_KERNELS, rtx_capi.hip), k_aov and the variance of an adaptive film's estimate.
+// (RTX_DENOISE_AOV_KERNELS, rtx_queries.hip), k_aov.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -76,31 +76,6 @@ __global__ __launch_bounds__(kBlock, kTraceWaves) void k_aov(DScene S, rtx_camer
   if (albedo) albedo[3 * p] = a.x, albedo[3 * p + 1] = a.y, albedo[3 * p + 2] = a.z;
   if (normal) normal[3 * p] = n.x, normal[3 * p + 1] = n.y, normal[3 * p + 2] = n.z;
   if (depth) depth[p] = t;
-}
-
-// The variance of an adaptive film's per-pixel estimate from its running M2, as one luminance
-// figure: var_c = m2_c / (n - 1) / n (0 below two samples), var = sum_c lumweight_c^2 var_c; with
-// `demodulate`, divided by lum(max(albedo, floor))^2 of the film's f32 albedo record (the colour
-// the filter sees is divided by that albedo).
-__global__ __launch_bounds__(kBlock) void k_film_variance(PixelSoA px, int64_t npix, const float4* __restrict__ albedo,
-                                                          int demodulate, double* __restrict__ var) {
-  const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (p >= npix) return;
-  const int n = px.samples[p];
-  double v = 0.0;
-  if (n >= 2) {
-    const double vr = (px.m2[p] / (double)(n - 1)) / (double)n;
-    const double vg = (px.m2[npix + p] / (double)(n - 1)) / (double)n;
-    const double vb = (px.m2[2 * npix + p] / (double)(n - 1)) / (double)n;
-    v = ((0.2126 * 0.2126) * vr + (0.7152 * 0.7152) * vg) + (0.0722 * 0.0722) * vb;
-    if (demodulate) {
-      const float4 a = albedo[p];
-      const double l = (0.2126 * (double)fmaxf(a.x, rtxdn::kAlbedoFloor) + 0.7152 * (double)fmaxf(a.y, rtxdn::kAlbedoFloor)) +
-                       0.0722 * (double)fmaxf(a.z, rtxdn::kAlbedoFloor);
-      v = v / (l * l);
-    }
-  }
-  var[p] = v;
 }
 
 }  // namespace rtxd

@@ -16,7 +16,7 @@
 
 // Per-translation-unit choices.  rtx_park.hip, which compiles the PARK instantiations of
 // k_persistent and nothing else, defines RTX_PARK_TU 1 before including this file; every
-// other translation unit (rtx_capi.hip: the plain kernel, the frame kernels) takes the plain
+// other translation unit (rtx_capi.hip: the plain kernel, the frame kernels; rtx_queries.hip: the query kernels) takes the plain
 // kernel's choices.  Each was picked by A/B on the scenes that run that TU's kernels (DESIGN.md
 // ledger); register allocation decides which is best per kernel.  k_persistent asserts that
 // its PARK instantiations come from the PARK TU only.

@@ -1,6 +1,6 @@
 // rtx_direct.h — direct-lighting queries: the scene's emitters sampled from caller-supplied
 // surface points (rtx_direct*, rtx_scene_emitters, include/rtx.h; DESIGN.md §4g "Direct-lighting
-// queries").  Included once, by rtx_capi.hip, after rtx_irradiance.h.  Nothing here is used by a
+// queries").  Included once, by rtx_queries.hip, after rtx_irradiance.h.  Nothing here is used by a
 // render kernel, and trace<>(), shade*, k_radiance*, k_irradiance, k_ao and k_occluded are as
 // they were: the kernels below call the same device functions.
 //

@@ -9,6 +9,7 @@
 #include <cstring>
 #include <string>
 
+#include "rtx_denoise.h"
 #include "rtx_kernels.h"
 
 namespace rtxd {
@@ -141,6 +142,30 @@ __global__ __launch_bounds__(kBlock) void k_film_pack(PixelSoA px, FilmBody b, i
       px.conv[i] = adaptive ? (uint8_t)(b.conv[i] != 0) : (uint8_t)0;
     }
   }
+}
+// The variance of an adaptive film's per-pixel estimate from its running M2, as one luminance
+// figure: var_c = m2_c / (n - 1) / n (0 below two samples), var = sum_c lumweight_c^2 var_c; with
+// `demodulate`, divided by lum(max(albedo, floor))^2 of the film's f32 albedo record (the colour
+// the filter sees is divided by that albedo).
+__global__ __launch_bounds__(kBlock) void k_film_variance(PixelSoA px, int64_t npix, const float4* __restrict__ albedo,
+                                                          int demodulate, double* __restrict__ var) {
+  const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (p >= npix) return;
+  const int n = px.samples[p];
+  double v = 0.0;
+  if (n >= 2) {
+    const double vr = (px.m2[p] / (double)(n - 1)) / (double)n;
+    const double vg = (px.m2[npix + p] / (double)(n - 1)) / (double)n;
+    const double vb = (px.m2[2 * npix + p] / (double)(n - 1)) / (double)n;
+    v = ((0.2126 * 0.2126) * vr + (0.7152 * 0.7152) * vg) + (0.0722 * 0.0722) * vb;
+    if (demodulate) {
+      const float4 a = albedo[p];
+      const double l = (0.2126 * (double)fmaxf(a.x, rtxdn::kAlbedoFloor) + 0.7152 * (double)fmaxf(a.y, rtxdn::kAlbedoFloor)) +
+                       0.0722 * (double)fmaxf(a.z, rtxdn::kAlbedoFloor);
+      v = v / (l * l);
+    }
+  }
+  var[p] = v;
 }
 #endif  // __HIPCC__
 

@@ -684,4 +684,21 @@ __global__ __launch_bounds__(kBlock) void k_resolve(PixelSoA px, int64_t npix, i
   if (spp_out) spp_out[p] = megakernel == 1 ? spp : n;
 }
 
+// Test hook (rtx_internal_camera_rays): the primary rays the render kernels generate, one lane
+// per (pixel of the subset, sample), pixel major: k_wf_generate's get_ray with
+// make_rng(seed, global pixel, sample, 0).  out: 6 doubles per ray (origin, direction).
+__global__ __launch_bounds__(kBlock) void k_camera_rays(rtx_camera cam, PixelMap map, uint32_t nslots, uint32_t K,
+                                                        uint64_t seed, int32_t s0, double* __restrict__ out) {
+  const uint32_t j = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
+  if (j >= nslots) return;
+  const uint32_t p = j / K, k = j - p * K;
+  int x, y;
+  map.xy(p, x, y);
+  Rng g = make_rng(seed, (uint32_t)(y * map.W + x), (uint32_t)s0 + k, 0u);
+  V3 o, d;
+  get_ray(cam, x, y, g, o, d);
+  double* q = out + 6 * (uint64_t)j;
+  q[0] = o.x, q[1] = o.y, q[2] = o.z, q[3] = d.x, q[4] = d.y, q[5] = d.z;
+}
+
 }  // namespace rtxd

@@ -1,6 +1,6 @@
 // rtx_irradiance.h — irradiance queries: the cosine-weighted gather of radiance over the
 // hemisphere at caller-supplied surface points (rtx_irradiance*, include/rtx.h; DESIGN.md §4f
-// "Irradiance queries").  Included once, by rtx_capi.hip, after rtx_radiance.h.  Nothing here is
+// "Irradiance queries").  Included once, by rtx_queries.hip, after rtx_radiance.h.  Nothing here is
 // used by a render kernel, and k_radiance, k_radiance_sum, k_ao and trace<>() are as they were:
 // the kernels below call the same device functions.
 //

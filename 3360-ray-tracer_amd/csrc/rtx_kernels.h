@@ -1,4 +1,4 @@
-// rtx_kernels.h — HIP kernels of the hot path (included once, by rtx_capi.hip).
+// rtx_kernels.h — HIP kernels of the hot path (included by rtx_capi.hip, rtx_queries.hip and rtx_park.hip: templates only).
 //
 //   k_intersect        RayIntegrator::IntersectBatch seam (one ray per lane)
 //   k_wf_generate      WavefrontRenderer primary generation (wavefront.cc:62-79)

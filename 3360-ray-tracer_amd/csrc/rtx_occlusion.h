@@ -1,6 +1,6 @@
 // rtx_occlusion.h — occlusion (any-hit) ray queries and the ambient-occlusion pass
 // (rtx_occluded*, rtx_ao*, include/rtx.h; DESIGN.md §4d "Occlusion queries and the AO pass").
-// Included once, by rtx_capi.hip, after the trace kernels.  Nothing here is used by a render
+// Included once, by rtx_queries.hip, after the trace kernels.  Nothing here is used by a render
 // kernel: k_persistent, k_wf_extend, k_intersect and trace<>() are as they were.
 //
 // Contract: occluded(ray) == 1 iff some primitive's own test (prim_t: the sphere, triangle and

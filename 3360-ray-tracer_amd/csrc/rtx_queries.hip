@@ -1,0 +1,461 @@
+// rtx_queries.hip — the ray-query entry points of the C ABI (include/rtx.h) and their kernels:
+// closest hit (rtx_intersect*), any hit and the AO pass (rtx_occluded*, rtx_ao*), first-hit AOVs
+// (rtx_aov*), radiance, irradiance and direct lighting on caller-supplied rays and surfels
+// (rtx_radiance*, rtx_irradiance*, rtx_direct*, rtx_scene_emitters), with their test hooks.
+// Scenes, films and the frame renderer are rtx_capi.hip's; the two share rtx_host.h.  Every query
+// picks its walk with with_walk (fast only with a fast tree, the scene's stack size).
+#include <atomic>
+#include <cstring>
+
+#include "rtx_host.h"
+#include "rtx_occlusion.h"
+#include "rtx_radiance.h"
+#include "rtx_irradiance.h"
+#include "rtx_direct.h"
+#define RTX_DENOISE_AOV_KERNELS  // this translation unit holds k_aov (it needs the trace kernels)
+#include "rtx_denoise.h"
+
+// k_aov over a pixel map, with the walk rtx_intersect_device picks for `precision`
+int aov_on(rtx_scene* sc, const rtx_camera* cam, const PixelMap& map, int64_t npix, int32_t precision, double* d_albedo,
+           double* d_normal, double* d_depth, hipStream_t s) {
+  if (npix == 0) return RTX_OK;
+  return with_walk(sc, precision, [&](auto w) {
+    return launch_1d(k_aov<w.stack, w.fast>, npix, stack_lds_bytes(w.stack), s, sc->S, *cam, map, npix,
+                     (double)RTX_SEAM_TMIN, d_albedo, d_normal, d_depth);
+  });
+}
+
+namespace {
+// ---- direct-lighting queries (rtx_direct.h) ----
+EmitterTable emitter_table(const rtx_scene* sc) {
+  return EmitterTable{sc->emit_prim.as<uint32_t>(), sc->emit_cum.as<double>(), (int64_t)sc->emit_idx.size()};
+}
+}  // namespace
+// The emitters' areas and their running sum from the live primitives, on `s`: at create, and at
+// the end of every in-place update.  A scene without emitters launches nothing.
+int emitters_rebuild(rtx_scene* sc, hipStream_t s) {
+  const EmitterTable E = emitter_table(sc);
+  if (E.n <= 0) return RTX_OK;
+  int rc;
+  if ((rc = launch_1d(k_emitter_area, E.n, 0, s, sc->prims.as<rtx_prim>(), E))) return rc;
+  return launch_1d(k_emitter_scan, 1, 0, s, E);
+}
+
+namespace {
+// ---- occlusion queries and the AO pass (rtx_occlusion.h) ----
+// rays == nullptr: k_ao into d_out; else k_ao_rays (the test hook's sample rays)
+int ao_on(rtx_scene* sc, const rtx_camera* cam, const PixelMap& map, int64_t npix, int32_t precision,
+          const rtx_ao_params* ao, double* d_out, rtx_ray* d_rays, hipStream_t s) {
+  if (npix == 0) return RTX_OK;
+  return with_walk(sc, precision, [&](auto w) {
+    if (d_rays)
+      return launch_1d(k_ao_rays<w.stack, w.fast>, npix, stack_lds_bytes(w.stack), s, sc->S, *cam, map, npix, ao->seed,
+                       ao->samples, d_rays);
+    return launch_1d(k_ao<w.stack, w.fast>, npix, stack_lds_bytes(w.stack), s, sc->S, *cam, map, npix, ao->seed,
+                     ao->samples, ao->radius, d_out);
+  });
+}
+// the checks rtx_ao, rtx_ao_device and rtx_internal_ao_rays share; *npix: pixels of the subset
+int ao_check(const rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, const rtx_ao_params* ao,
+             PixelMap& map, int64_t* npix) {
+  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
+  if (!cam || !prm || !ao) return fail(RTX_ERR_INVALID, "NULL argument");
+  if (ao->samples < 1 || ao->samples > 1024) return fail(RTX_ERR_INVALID, "ao: samples outside 1..1024");
+  if (!(ao->radius > 0)) return fail(RTX_ERR_INVALID, "ao: radius must be positive");
+  std::string err;
+  *npix = subset_pixels(cam, prm, map, err);
+  if (*npix < 0) return fail(RTX_ERR_INVALID, err);
+  return RTX_OK;
+}
+// ---- radiance queries (rtx_radiance.h) ----
+// the slot cap of the calls that follow (rtx_internal_radiance_chunk; 0: kRadianceSlots)
+std::atomic<int64_t> g_radiance_chunk{0};
+// what a chunk's slots hold (radiance_on): a path from a caller's ray, a path from a surfel's
+// hemisphere sample, or a surfel's emitter sample
+enum SlotKind { kSlotRadiance = 0, kSlotIrradiance = 1, kSlotDirect = 2 };
+// the checks rtx_radiance*, rtx_irradiance*, rtx_direct* and their test hooks share, in the documented order
+int radiance_check(const rtx_scene* sc, const rtx_radiance_params* prm, const void* rays, const void* out) {
+  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
+  if (!prm) return fail(RTX_ERR_INVALID, "NULL argument");
+  if (!rays || !out) return fail(RTX_ERR_INVALID, "NULL buffer");
+  if (prm->spp < 1) return fail(RTX_ERR_INVALID, "radiance: spp must be at least 1");
+  if (prm->first_sample < 0 || prm->first_sample > 0x7FFFFFFF - prm->spp)
+    return fail(RTX_ERR_INVALID, "radiance: first_sample must be >= 0 and first_sample + spp fit int32");
+  if (prm->max_depth < 0) return fail(RTX_ERR_INVALID, "negative max_depth");
+  if (prm->precision != RTX_PREC_PARITY && prm->precision != RTX_PREC_FAST)
+    return fail(RTX_ERR_INVALID, "radiance: bad precision");
+  return RTX_OK;
+}
+// n > 0 rays on device buffers, in chunks of at most `cap` slots (ray x sample): whole rays per
+// chunk, or, when one ray's samples exceed the cap, one ray at a time in runs of `cap` samples
+// whose partial sum k_radiance_sum carries.  id_base: the pixel key of d_rays[0] when d_ids is
+// null (the host entry point's batches).  what: for kSlotIrradiance and kSlotDirect d_rays are
+// surfels and the slots are k_irradiance's (rtx_irradiance*) or k_direct's (rtx_direct*: a
+// slot's "segments" are its visibility, 0 or 1); the chunking, the scratch and the sum are the same.
+int radiance_on(rtx_scene* sc, const rtx_ray* d_rays, const uint32_t* d_ids, uint64_t id_base, int64_t n,
+                const rtx_radiance_params* prm, double* d_out, uint32_t* d_segs, hipStream_t s,
+                SlotKind what = kSlotRadiance) {
+  const int64_t tuned = g_radiance_chunk.load();
+  const int64_t cap = std::min<int64_t>(tuned > 0 ? tuned : kRadianceSlots, kRadianceSlotsMax);
+  const int64_t spp = prm->spp;
+  const int64_t rays_per = std::max<int64_t>(1, cap / spp);  // rays per chunk
+  const int64_t k_per = std::min<int64_t>(spp, cap);         // samples of a ray per chunk
+  const int64_t most = std::min<int64_t>(n, rays_per) * k_per;  // slots of the largest chunk (<= cap)
+  int rc;
+  if ((rc = sc->rad_L.reserve((size_t)most * 3 * sizeof(double)))) return rc;
+  if ((rc = sc->rad_segs.reserve((size_t)most * sizeof(uint32_t)))) return rc;
+  if (k_per < spp) {  // (one ray per chunk)
+    if ((rc = sc->rad_carry.reserve(4 * sizeof(double)))) return rc;
+  }
+  double* const carry = k_per < spp ? sc->rad_carry.as<double>() : nullptr;
+  return with_walk(sc, prm->precision, [&](auto w) {
+    constexpr size_t lds = stack_lds_bytes(w.stack);
+    for (int64_t r0 = 0; r0 < n; r0 += rays_per) {
+      const int64_t nr = std::min<int64_t>(rays_per, n - r0);
+      for (int64_t k0 = 0; k0 < spp; k0 += k_per) {
+        const int64_t K = std::min<int64_t>(k_per, spp - k0);
+        RadianceChunk A;
+        A.rays = d_rays, A.ids = d_ids, A.ray0 = r0, A.id_base = id_base;
+        A.slots = (uint32_t)(nr * K), A.K = (uint32_t)K;
+        A.s0 = (int32_t)(prm->first_sample + k0), A.max_depth = prm->max_depth, A.seed = prm->seed;
+        A.L = sc->rad_L.as<double>(), A.segs = sc->rad_segs.as<uint32_t>();
+        switch (what) {
+          case kSlotDirect: rc = launch_1d(k_direct<w.stack, w.fast>, A.slots, lds, s, sc->S, emitter_table(sc), A); break;
+          case kSlotIrradiance: rc = launch_1d(k_irradiance<w.stack, w.fast>, A.slots, lds, s, sc->S, A); break;
+          default: rc = launch_1d(k_radiance<w.stack, w.fast>, A.slots, lds, s, sc->S, A);
+        }
+        if (rc) return rc;
+        if ((rc = launch_1d(k_radiance_sum, nr, 0, s, sc->rad_L.as<double>(), sc->rad_segs.as<uint32_t>(), nr,
+                            (uint32_t)K, k0 == 0 ? 1 : 0, k0 + K == spp ? 1 : 0, prm->spp, carry,
+                            carry ? (uint32_t*)(carry + 3) : nullptr, d_out + 3 * r0, d_segs ? d_segs + r0 : nullptr)))
+          return rc;
+      }
+    }
+    return (int)RTX_OK;
+  });
+}
+// The host entry point works in batches of kRadianceHostRays rays: the caller's rays and ids are
+// copied into pinned memory, traced, and the results copied back out of it.
+constexpr size_t kRadianceHostRays = (size_t)1 << 20;
+// (shared with rtx_irradiance and rtx_direct, whose rays are surfels)
+int radiance_host(rtx_scene* sc, const rtx_ray* rays, const uint32_t* ids, size_t n, const rtx_radiance_params* prm,
+                  double* out_rgb, uint32_t* out_segments, SlotKind what) {
+  int rc;
+  if ((rc = radiance_check(sc, prm, rays, out_rgb))) return rc;
+  if (n == 0) return RTX_OK;
+  HIPC(hipSetDevice(sc->device));
+  const size_t m = std::min(n, kRadianceHostRays);
+  // pinned: rays | rgb | ids | segments (8-byte items first)
+  const size_t off_rgb = m * sizeof(rtx_ray), off_ids = off_rgb + m * 3 * sizeof(double),
+               off_seg = off_ids + m * sizeof(uint32_t);
+  if ((rc = sc->rad_host.reserve(off_seg + m * sizeof(uint32_t)))) return rc;
+  if ((rc = sc->rays.reserve(m * sizeof(rtx_ray)))) return rc;
+  if ((rc = sc->rad_out.reserve(m * 3 * sizeof(double)))) return rc;
+  if ((rc = sc->rad_oseg.reserve(m * sizeof(uint32_t)))) return rc;
+  if (ids && (rc = sc->rad_ids.reserve(m * sizeof(uint32_t)))) return rc;
+  char* const pin = (char*)sc->rad_host.p;
+  for (size_t b0 = 0; b0 < n; b0 += m) {
+    const size_t nb = std::min(m, n - b0);
+    std::memcpy(pin, rays + b0, nb * sizeof(rtx_ray));
+    HIPC(hipMemcpyAsync(sc->rays.p, pin, nb * sizeof(rtx_ray), hipMemcpyHostToDevice, sc->stream));
+    if (ids) {
+      std::memcpy(pin + off_ids, ids + b0, nb * sizeof(uint32_t));
+      HIPC(hipMemcpyAsync(sc->rad_ids.p, pin + off_ids, nb * sizeof(uint32_t), hipMemcpyHostToDevice, sc->stream));
+    }
+    if ((rc = radiance_on(sc, sc->rays.as<rtx_ray>(), ids ? sc->rad_ids.as<uint32_t>() : nullptr, (uint64_t)b0,
+                          (int64_t)nb, prm, sc->rad_out.as<double>(), sc->rad_oseg.as<uint32_t>(), sc->stream, what)))
+      return rc;
+    HIPC(hipMemcpyAsync(pin + off_rgb, sc->rad_out.p, nb * 3 * sizeof(double), hipMemcpyDeviceToHost, sc->stream));
+    if (out_segments)
+      HIPC(hipMemcpyAsync(pin + off_seg, sc->rad_oseg.p, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, sc->stream));
+    HIPC(hipStreamSynchronize(sc->stream));
+    std::memcpy(out_rgb + 3 * b0, pin + off_rgb, nb * 3 * sizeof(double));
+    if (out_segments) std::memcpy(out_segments + b0, pin + off_seg, nb * sizeof(uint32_t));
+  }
+  return RTX_OK;
+}
+// the device entry points of the three families: the checks, then the chunks on the caller's stream
+int radiance_device(rtx_scene* sc, const rtx_ray* d_rays, const uint32_t* d_ids, size_t n,
+                    const rtx_radiance_params* prm, double* d_out_rgb, uint32_t* d_out_segments, void* stream,
+                    SlotKind what) {
+  int rc;
+  if ((rc = radiance_check(sc, prm, d_rays, d_out_rgb))) return rc;
+  if (n == 0) return RTX_OK;
+  HIPC(hipSetDevice(sc->device));
+  return radiance_on(sc, d_rays, d_ids, 0, (int64_t)n, prm, d_out_rgb, d_out_segments,
+                     stream ? (hipStream_t)stream : sc->stream, what);
+}
+// What rtx_internal_irradiance_rays and rtx_internal_direct_samples share: the checks, the
+// surfels and ids staged to the device, `launch(nslots, d_surfels, d_ids, d_out)` into the slot
+// scratch (`per_slot` doubles per slot) and the copy back to the host.
+template <class Launch>
+int surfel_samples(rtx_scene* sc, const rtx_ray* surfels, const uint32_t* ids, size_t n, const rtx_radiance_params* prm,
+                   double* out, size_t per_slot, const char* too_many, Launch launch) {
+  int rc;
+  if ((rc = radiance_check(sc, prm, surfels, out))) return rc;
+  if (n == 0) return RTX_OK;
+  if (n > (size_t)kRadianceSlotsMax || (int64_t)n * prm->spp > kRadianceSlotsMax) return fail(RTX_ERR_INVALID, too_many);
+  HIPC(hipSetDevice(sc->device));
+  const uint32_t nslots = (uint32_t)(n * (size_t)prm->spp);
+  const size_t bytes = (size_t)nslots * per_slot * sizeof(double);
+  if ((rc = sc->rays.reserve(n * sizeof(rtx_ray)))) return rc;
+  if ((rc = sc->rad_L.reserve(bytes))) return rc;
+  if (ids && (rc = sc->rad_ids.reserve(n * sizeof(uint32_t)))) return rc;
+  HIPC(hipMemcpyAsync(sc->rays.p, surfels, n * sizeof(rtx_ray), hipMemcpyHostToDevice, sc->stream));
+  if (ids) HIPC(hipMemcpyAsync(sc->rad_ids.p, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, sc->stream));
+  if ((rc = launch(nslots, sc->rays.as<rtx_ray>(), ids ? sc->rad_ids.as<uint32_t>() : nullptr, sc->rad_L.as<double>())))
+    return rc;
+  HIPC(hipMemcpyAsync(out, sc->rad_L.p, bytes, hipMemcpyDeviceToHost, sc->stream));
+  HIPC(hipStreamSynchronize(sc->stream));
+  return RTX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int rtx_intersect_device(rtx_scene* sc, const rtx_ray* d_rays, size_t n, rtx_hit* d_hits, double tmin, double tmax,
+                         int32_t precision, void* stream) {
+  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
+  if (n == 0) return RTX_OK;
+  if (!d_rays || !d_hits) return fail(RTX_ERR_INVALID, "NULL buffer");
+  HIPC(hipSetDevice(sc->device));
+  hipStream_t s = stream ? (hipStream_t)stream : sc->stream;
+  return with_walk(sc, precision, [&](auto w) {
+    return launch_1d(k_intersect<w.stack, w.fast>, (int64_t)n, stack_lds_bytes(w.stack), s, sc->S, d_rays, (int64_t)n,
+                     d_hits, tmin, tmax);
+  });
+}
+
+int rtx_intersect(rtx_scene* sc, const rtx_ray* rays, size_t n, rtx_hit* hits, double tmin, double tmax,
+                  int32_t precision) {
+  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
+  if (n == 0) return RTX_OK;
+  if (!rays || !hits) return fail(RTX_ERR_INVALID, "NULL buffer");
+  HIPC(hipSetDevice(sc->device));
+  int rc;
+  if ((rc = sc->rays.reserve(n * sizeof(rtx_ray)))) return rc;
+  if ((rc = sc->hits.reserve(n * sizeof(rtx_hit)))) return rc;
+  HIPC(hipMemcpyAsync(sc->rays.p, rays, n * sizeof(rtx_ray), hipMemcpyHostToDevice, sc->stream));
+  if ((rc = rtx_intersect_device(sc, sc->rays.as<rtx_ray>(), n, sc->hits.as<rtx_hit>(), tmin, tmax, precision,
+                                 sc->stream)))
+    return rc;
+  HIPC(hipMemcpyAsync(hits, sc->hits.p, n * sizeof(rtx_hit), hipMemcpyDeviceToHost, sc->stream));
+  HIPC(hipStreamSynchronize(sc->stream));
+  return RTX_OK;
+}
+
+int rtx_occluded_device(rtx_scene* sc, const rtx_ray* d_rays, size_t n, uint8_t* d_out, double tmin, double tmax,
+                        int32_t precision, void* stream) {
+  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
+  if (!(tmin < tmax)) return fail(RTX_ERR_INVALID, "occluded: tmin must be below tmax");
+  if (n == 0) return RTX_OK;
+  if (!d_rays || !d_out) return fail(RTX_ERR_INVALID, "NULL buffer");
+  HIPC(hipSetDevice(sc->device));
+  hipStream_t s = stream ? (hipStream_t)stream : sc->stream;
+  return with_walk(sc, precision, [&](auto w) {
+    return launch_1d(k_occluded<w.stack, w.fast>, (int64_t)n, stack_lds_bytes(w.stack), s, sc->S, d_rays, (int64_t)n,
+                     d_out, tmin, tmax);
+  });
+}
+
+int rtx_occluded(rtx_scene* sc, const rtx_ray* rays, size_t n, uint8_t* out, double tmin, double tmax,
+                 int32_t precision) {
+  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
+  if (!(tmin < tmax)) return fail(RTX_ERR_INVALID, "occluded: tmin must be below tmax");
+  if (n == 0) return RTX_OK;
+  if (!rays || !out) return fail(RTX_ERR_INVALID, "NULL buffer");
+  HIPC(hipSetDevice(sc->device));
+  int rc;
+  if ((rc = sc->rays.reserve(n * sizeof(rtx_ray)))) return rc;
+  if ((rc = sc->occ.reserve(n))) return rc;
+  HIPC(hipMemcpyAsync(sc->rays.p, rays, n * sizeof(rtx_ray), hipMemcpyHostToDevice, sc->stream));
+  if ((rc = rtx_occluded_device(sc, sc->rays.as<rtx_ray>(), n, sc->occ.as<uint8_t>(), tmin, tmax, precision, sc->stream)))
+    return rc;
+  HIPC(hipMemcpyAsync(out, sc->occ.p, n, hipMemcpyDeviceToHost, sc->stream));
+  HIPC(hipStreamSynchronize(sc->stream));
+  return RTX_OK;
+}
+
+int rtx_ao_device(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, const rtx_ao_params* ao,
+                  double* d_out, void* stream) {
+  PixelMap map;
+  int64_t npix;
+  int rc;
+  if ((rc = ao_check(sc, cam, prm, ao, map, &npix))) return rc;
+  if (npix == 0) return RTX_OK;
+  if (!d_out) return fail(RTX_ERR_INVALID, "NULL buffer");
+  HIPC(hipSetDevice(sc->device));
+  return ao_on(sc, cam, map, npix, prm->precision, ao, d_out, nullptr, stream ? (hipStream_t)stream : sc->stream);
+}
+
+int rtx_ao(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, const rtx_ao_params* ao, double* out) {
+  PixelMap map;
+  int64_t npix;
+  int rc;
+  if ((rc = ao_check(sc, cam, prm, ao, map, &npix))) return rc;
+  if (npix == 0) return RTX_OK;
+  if (!out) return fail(RTX_ERR_INVALID, "NULL buffer");
+  HIPC(hipSetDevice(sc->device));
+  if ((rc = sc->aov_f64.reserve((size_t)npix * sizeof(double)))) return rc;  // (the AOV staging: one double per pixel)
+  if ((rc = ao_on(sc, cam, map, npix, prm->precision, ao, sc->aov_f64.as<double>(), nullptr, sc->stream))) return rc;
+  HIPC(hipMemcpyAsync(out, sc->aov_f64.p, (size_t)npix * sizeof(double), hipMemcpyDeviceToHost, sc->stream));
+  HIPC(hipStreamSynchronize(sc->stream));
+  return RTX_OK;
+}
+
+// Test hook (not in rtx.h): the sample rays of rtx_ao for the same arguments, npix * samples of
+// them, pixel major, made by the device function k_ao calls (ao_direction after ao_first_hit,
+// rtx_occlusion.h) and copied to the host; a pixel that misses has all-zero rays.
+int rtx_internal_ao_rays(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, const rtx_ao_params* ao,
+                         rtx_ray* out) {
+  PixelMap map;
+  int64_t npix;
+  int rc;
+  if ((rc = ao_check(sc, cam, prm, ao, map, &npix))) return rc;
+  if (npix == 0) return RTX_OK;
+  if (!out) return fail(RTX_ERR_INVALID, "NULL buffer");
+  HIPC(hipSetDevice(sc->device));
+  const size_t bytes = (size_t)npix * (size_t)ao->samples * sizeof(rtx_ray);
+  if ((rc = sc->rays.reserve(bytes))) return rc;
+  if ((rc = ao_on(sc, cam, map, npix, prm->precision, ao, nullptr, sc->rays.as<rtx_ray>(), sc->stream))) return rc;
+  HIPC(hipMemcpyAsync(out, sc->rays.p, bytes, hipMemcpyDeviceToHost, sc->stream));
+  HIPC(hipStreamSynchronize(sc->stream));
+  return RTX_OK;
+}
+
+int rtx_aov_device(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, double* d_albedo,
+                   double* d_normal, double* d_depth, void* stream) {
+  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
+  if (!cam || !prm) return fail(RTX_ERR_INVALID, "NULL argument");
+  PixelMap map;
+  std::string err;
+  const int64_t npix = subset_pixels(cam, prm, map, err);
+  if (npix < 0) return fail(RTX_ERR_INVALID, err);
+  HIPC(hipSetDevice(sc->device));
+  return aov_on(sc, cam, map, npix, prm->precision, d_albedo, d_normal, d_depth, stream ? (hipStream_t)stream : sc->stream);
+}
+
+int rtx_aov(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, double* albedo, double* normal,
+            double* depth) {
+  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
+  if (!cam || !prm) return fail(RTX_ERR_INVALID, "NULL argument");
+  PixelMap map;
+  std::string err;
+  const int64_t npix = subset_pixels(cam, prm, map, err);
+  if (npix < 0) return fail(RTX_ERR_INVALID, err);
+  if (npix == 0) return RTX_OK;
+  HIPC(hipSetDevice(sc->device));
+  int rc;
+  if ((rc = sc->aov_f64.reserve((size_t)npix * 7 * sizeof(double)))) return rc;
+  double* a = sc->aov_f64.as<double>();  // albedo 3 n, normal 3 n, depth n
+  double *n = a + 3 * npix, *d = a + 6 * npix;
+  hipStream_t s = sc->stream;
+  if ((rc = aov_on(sc, cam, map, npix, prm->precision, albedo ? a : nullptr, normal ? n : nullptr, depth ? d : nullptr, s)))
+    return rc;
+  if (albedo) HIPC(hipMemcpyAsync(albedo, a, (size_t)npix * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (normal) HIPC(hipMemcpyAsync(normal, n, (size_t)npix * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (depth) HIPC(hipMemcpyAsync(depth, d, (size_t)npix * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPC(hipStreamSynchronize(s));
+  return RTX_OK;
+}
+
+int rtx_radiance_device(rtx_scene* sc, const rtx_ray* d_rays, const uint32_t* d_ids, size_t n,
+                        const rtx_radiance_params* prm, double* d_out_rgb, uint32_t* d_out_segments, void* stream) {
+  return radiance_device(sc, d_rays, d_ids, n, prm, d_out_rgb, d_out_segments, stream, kSlotRadiance);
+}
+int rtx_radiance(rtx_scene* sc, const rtx_ray* rays, const uint32_t* ids, size_t n, const rtx_radiance_params* prm,
+                 double* out_rgb, uint32_t* out_segments) {
+  return radiance_host(sc, rays, ids, n, prm, out_rgb, out_segments, kSlotRadiance);
+}
+
+// ---- irradiance queries (rtx_irradiance.h): rtx_radiance's checks, chunks and staging ----
+int rtx_irradiance_device(rtx_scene* sc, const rtx_ray* d_surfels, const uint32_t* d_ids, size_t n,
+                          const rtx_radiance_params* prm, double* d_out_rgb, uint32_t* d_out_segments, void* stream) {
+  return radiance_device(sc, d_surfels, d_ids, n, prm, d_out_rgb, d_out_segments, stream, kSlotIrradiance);
+}
+int rtx_irradiance(rtx_scene* sc, const rtx_ray* surfels, const uint32_t* ids, size_t n,
+                   const rtx_radiance_params* prm, double* out_rgb, uint32_t* out_segments) {
+  return radiance_host(sc, surfels, ids, n, prm, out_rgb, out_segments, kSlotIrradiance);
+}
+
+// Test hook (not in rtx.h): the depth-0 segments rtx_irradiance traces for the same arguments
+// (seed, first_sample and spp of prm are read; the rest is checked as there), n x spp x 6
+// doubles (origin, direction), surfel major, made by the device function k_irradiance calls
+// (irradiance_ray, rtx_irradiance.h); all zero for a surfel with a degenerate normal.  Host
+// buffers.
+int rtx_internal_irradiance_rays(rtx_scene* sc, const rtx_ray* surfels, const uint32_t* ids, size_t n,
+                                 const rtx_radiance_params* prm, double* out) {
+  return surfel_samples(sc, surfels, ids, n, prm, out, 6, "irradiance rays: too many rays for one call",
+                        [&](uint32_t nslots, const rtx_ray* d_surfels, const uint32_t* d_ids, double* d_out) {
+                          return launch_1d(k_irradiance_rays, nslots, 0, sc->stream, d_surfels, d_ids, nslots,
+                                           (uint32_t)prm->spp, prm->seed, prm->first_sample, d_out);
+                        });
+}
+
+// ---- direct-lighting queries (rtx_direct.h): rtx_radiance's checks, chunks and staging ----
+int rtx_direct_device(rtx_scene* sc, const rtx_ray* d_surfels, const uint32_t* d_ids, size_t n,
+                      const rtx_radiance_params* prm, double* d_out_rgb, uint32_t* d_out_visible, void* stream) {
+  return radiance_device(sc, d_surfels, d_ids, n, prm, d_out_rgb, d_out_visible, stream, kSlotDirect);
+}
+int rtx_direct(rtx_scene* sc, const rtx_ray* surfels, const uint32_t* ids, size_t n, const rtx_radiance_params* prm,
+               double* out_rgb, uint32_t* out_visible) {
+  return radiance_host(sc, surfels, ids, n, prm, out_rgb, out_visible, kSlotDirect);
+}
+
+int rtx_scene_emitters(const rtx_scene* sc, int64_t* count, double* area) {
+  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
+  if (!count && !area) return fail(RTX_ERR_INVALID, "NULL argument");
+  const int64_t n = (int64_t)sc->emit_idx.size();
+  if (count) *count = n;
+  if (area) {
+    *area = 0.0;
+    if (n > 0) {
+      HIPC(hipSetDevice(sc->device));
+      HIPC(hipStreamSynchronize(sc->stream));
+      HIPC(hipMemcpy(area, sc->emit_cum.as<double>() + (n - 1), sizeof(double), hipMemcpyDeviceToHost));
+    }
+  }
+  return RTX_OK;
+}
+
+// Test hook (not in rtx.h): the samples rtx_direct draws for the same arguments (seed,
+// first_sample and spp of prm are read; the rest is checked as there), n x spp x 9 doubles
+// (segment origin, y - x, the unshadowed contribution C), surfel major, made by the device
+// function k_direct calls (direct_sample, rtx_direct.h); all zero where nothing is traced.  Host
+// buffers.
+int rtx_internal_direct_samples(rtx_scene* sc, const rtx_ray* surfels, const uint32_t* ids, size_t n,
+                                const rtx_radiance_params* prm, double* out) {
+  return surfel_samples(sc, surfels, ids, n, prm, out, 9, "direct samples: too many samples for one call",
+                        [&](uint32_t nslots, const rtx_ray* d_surfels, const uint32_t* d_ids, double* d_out) {
+                          return launch_1d(k_direct_samples, nslots, 0, sc->stream, sc->S, emitter_table(sc), d_surfels,
+                                           d_ids, nslots, (uint32_t)prm->spp, prm->seed, prm->first_sample, d_out);
+                        });
+}
+
+// Test hook (not in rtx.h): the live emitter table copied back after everything queued on the
+// scene's stream, at most `cap` entries: each emitter's primitive index (the caller's own order,
+// as rtx_scene_update_prims counts it) and the inclusive cumulative areas.  Either may be NULL.
+int rtx_internal_emitters(rtx_scene* sc, int64_t* prims_out, double* cum_out, int64_t cap) {
+  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
+  const int64_t n = std::min<int64_t>(std::max<int64_t>(0, cap), (int64_t)sc->emit_idx.size());
+  if (n == 0) return RTX_OK;
+  if (prims_out)
+    for (int64_t i = 0; i < n; i++) prims_out[i] = (int64_t)sc->emit_idx[(size_t)i];
+  if (cum_out) {
+    HIPC(hipSetDevice(sc->device));
+    HIPC(hipStreamSynchronize(sc->stream));
+    HIPC(hipMemcpy(cum_out, sc->emit_cum.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  return RTX_OK;
+}
+
+// Test hook (not in rtx.h): the slot cap of the radiance calls that follow in this process
+// (0 restores kRadianceSlots), so chunk seams are reached at small shapes.  Results never
+// depend on it.
+int rtx_internal_radiance_chunk(int64_t slots) {
+  if (slots < 0) return fail(RTX_ERR_INVALID, "radiance chunk: negative slot count");
+  g_radiance_chunk.store(slots);
+  return RTX_OK;
+}
+
+}  // extern "C"

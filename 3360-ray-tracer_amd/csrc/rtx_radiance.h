@@ -1,6 +1,6 @@
 // rtx_radiance.h — radiance queries: the bounce loop on caller-supplied rays (rtx_radiance*,
-// include/rtx.h; DESIGN.md §4e "Radiance queries").  Included once, by rtx_capi.hip, after the
-// frame kernels.  Nothing here is used by a render kernel: k_persistent, k_wf_*, k_intersect and
+// include/rtx.h; DESIGN.md §4e "Radiance queries").  Included once, by rtx_queries.hip, after the
+// trace kernels.  Nothing here is used by a render kernel: k_persistent, k_wf_*, k_intersect and
 // trace<>() are as they were; the kernels below call the same device functions.
 //
 // Contract: for ray i and sample k the lane traces the path the wavefront renderer traces from
@@ -11,7 +11,7 @@
 // the same operands, so the value equals the renderer's slot value bit for bit.
 #pragma once
 
-#include "rtx_frame_kernels.h"
+#include "rtx_kernels.h"
 
 namespace rtxd {
 
@@ -31,8 +31,6 @@ struct RadianceChunk {
   double* L;            // 3 doubles per slot
   uint32_t* segs;       // segments per slot
 };
-constexpr int64_t kRadianceSlots = (int64_t)1 << 24;     // a call's slot scratch: at most this many slots (448 MB)
-constexpr int64_t kRadianceSlotsMax = (int64_t)1 << 30;  // what rtx_internal_radiance_chunk may raise it to
 
 // One lane per slot: the whole path, the traversal stack in the lane's LDS column as in
 // k_intersect.  A lane whose path has ended idles until its wave's longest path ends (no refill).
@@ -99,23 +97,6 @@ __global__ __launch_bounds__(kBlock) void k_radiance_sum(const double* __restric
     for (int c = 0; c < 3; c++) carry[3 * r + c] = sum[c];
     carry_segs[r] = ns;
   }
-}
-
-// Test hook (rtx_internal_camera_rays): the primary rays the render kernels generate, one lane
-// per (pixel of the subset, sample), pixel major: k_wf_generate's get_ray with
-// make_rng(seed, global pixel, sample, 0).  out: 6 doubles per ray (origin, direction).
-__global__ __launch_bounds__(kBlock) void k_camera_rays(rtx_camera cam, PixelMap map, uint32_t nslots, uint32_t K,
-                                                        uint64_t seed, int32_t s0, double* __restrict__ out) {
-  const uint32_t j = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
-  if (j >= nslots) return;
-  const uint32_t p = j / K, k = j - p * K;
-  int x, y;
-  map.xy(p, x, y);
-  Rng g = make_rng(seed, (uint32_t)(y * map.W + x), (uint32_t)s0 + k, 0u);
-  V3 o, d;
-  get_ray(cam, x, y, g, o, d);
-  double* q = out + 6 * (uint64_t)j;
-  q[0] = o.x, q[1] = o.y, q[2] = o.z, q[3] = d.x, q[4] = d.y, q[5] = d.z;
 }
 
 }  // namespace rtxd
