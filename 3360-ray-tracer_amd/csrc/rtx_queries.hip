@@ -12,6 +12,7 @@
 #include "rtx_radiance.h"
 #include "rtx_irradiance.h"
 #include "rtx_direct.h"
+#include "rtx_shade_steps.h"
 #define RTX_DENOISE_AOV_KERNELS  // this translation unit holds k_aov (it needs the trace kernels)
 #include "rtx_denoise.h"
 
@@ -446,6 +447,56 @@ int rtx_internal_emitters(rtx_scene* sc, int64_t* prims_out, double* cum_out, in
     HIPC(hipStreamSynchronize(sc->stream));
     HIPC(hipMemcpy(cum_out, sc->emit_cum.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
   }
+  return RTX_OK;
+}
+
+// Test hook (not in rtx.h): one shading step per case (rtx_shade_steps.h), n ShadeCase in and n
+// ShadeRecord out, host buffers.  variant: 0 shade(); 1 shade_terminal (a case that does not end
+// on the sky gets cont = -1); 2 the scatter-API branch; 8 + bits: shade_core + shade_finish with
+// bit 0 LAMB, bit 1 NOTEX, bit 2 SET_ORIGIN = false (the hook sets the origin, as k_persistent
+// does).  A LAMB / NOTEX form on a scene whose flags do not allow it, and a material or primitive
+// index outside the scene's tables, are RTX_ERR_INVALID: nothing is launched.
+int rtx_internal_shade_steps(rtx_scene* sc, const void* cases, size_t n, int32_t variant, void* out) {
+  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
+  if (!cases || !out) return fail(RTX_ERR_INVALID, "NULL buffer");
+  if (!((variant >= 0 && variant <= 2) || (variant >= 8 && variant <= 15)))
+    return fail(RTX_ERR_INVALID, "shade steps: unknown variant");
+  if (n == 0) return RTX_OK;
+  if (n > (size_t)kRadianceSlots) return fail(RTX_ERR_INVALID, "shade steps: too many cases for one call");
+  const bool lamb = variant >= 8 && (variant & 1), notex = variant >= 8 && (variant & 2);
+  if (lamb && !sc->S.all_lambertian) return fail(RTX_ERR_INVALID, "shade steps: the scene is not all Lambertian");
+  if (notex && !sc->S.no_textures) return fail(RTX_ERR_INVALID, "shade steps: the scene reads textures");
+  const ShadeCase* cs = (const ShadeCase*)cases;
+  for (size_t i = 0; i < n; i++) {
+    if (cs[i].hit && (cs[i].mat < 0 || cs[i].mat >= sc->n_materials))
+      return fail(RTX_ERR_INVALID, "shade steps: material index out of range");
+    if (cs[i].lazy_uv < -1 || cs[i].lazy_uv >= sc->S.n_prims)
+      return fail(RTX_ERR_INVALID, "shade steps: primitive index out of range");
+  }
+  HIPC(hipSetDevice(sc->device));
+  int rc;
+  if ((rc = sc->rays.reserve(n * sizeof(ShadeCase)))) return rc;
+  if ((rc = sc->hits.reserve(n * sizeof(ShadeRecord)))) return rc;
+  HIPC(hipMemcpyAsync(sc->rays.p, cases, n * sizeof(ShadeCase), hipMemcpyHostToDevice, sc->stream));
+  const ShadeCase* d_in = sc->rays.as<ShadeCase>();
+  ShadeRecord* d_out = sc->hits.as<ShadeRecord>();
+  auto run = [&](auto kernel) { return launch_1d(kernel, (int64_t)n, 0, sc->stream, sc->S, d_in, (int64_t)n, d_out); };
+  switch (variant) {
+    case 0: rc = run(k_shade_steps<kShadeFormShade>); break;
+    case 1: rc = run(k_shade_steps<kShadeFormTerminal>); break;
+    case 2: rc = run(k_shade_steps<kShadeFormScatter>); break;
+    case 8: rc = run(k_shade_steps<kShadeFormCore, false, false, true>); break;
+    case 9: rc = run(k_shade_steps<kShadeFormCore, true, false, true>); break;
+    case 10: rc = run(k_shade_steps<kShadeFormCore, false, true, true>); break;
+    case 11: rc = run(k_shade_steps<kShadeFormCore, true, true, true>); break;
+    case 12: rc = run(k_shade_steps<kShadeFormCore, false, false, false>); break;
+    case 13: rc = run(k_shade_steps<kShadeFormCore, true, false, false>); break;
+    case 14: rc = run(k_shade_steps<kShadeFormCore, false, true, false>); break;
+    default: rc = run(k_shade_steps<kShadeFormCore, true, true, false>);
+  }
+  if (rc) return rc;
+  HIPC(hipMemcpyAsync(out, sc->hits.p, n * sizeof(ShadeRecord), hipMemcpyDeviceToHost, sc->stream));
+  HIPC(hipStreamSynchronize(sc->stream));
   return RTX_OK;
 }
 

@@ -776,6 +776,38 @@ def camera_rays(scene, cam, spp, seed=1234, first_sample=0, tile=None, stripes=N
     return out
 
 
+# rtx_internal_shade_steps (csrc/rtx_shade_steps.h): a case (hit record, path state, Philox key)
+# and the step's outcome
+SHADE_CASE_DTYPE = np.dtype([("p", "<f8", 3), ("normal", "<f8", 3), ("u", "<f8"), ("v", "<f8"), ("o", "<f8", 3),
+                             ("d", "<f8", 3), ("thr", "<f8", 3), ("seed", "<u8"), ("pixel", "<u4"), ("sample", "<u4"),
+                             ("hit", "<i4"), ("front_face", "<i4"), ("mat", "<i4"), ("depth", "<i4"),
+                             ("max_depth", "<i4"), ("lazy_uv", "<i4")])
+SHADE_RECORD_DTYPE = np.dtype([("L", "<f8", 3), ("o", "<f8", 3), ("d", "<f8", 3), ("thr", "<f8", 3), ("next", "<f8"),
+                               ("cont", "<i4"), ("depth", "<i4")])
+assert SHADE_CASE_DTYPE.itemsize == 176 and SHADE_RECORD_DTYPE.itemsize == 112
+# "core...": shade_core<LAMB, NOTEX, SET_ORIGIN> + shade_finish, the persistent kernel's form;
+# "_noorigin": SET_ORIGIN = false (the hook sets the child's origin, as that kernel does)
+SHADE_VARIANTS = {"shade": 0, "terminal": 1, "scatter": 2, "core": 8, "core_lamb": 9, "core_notex": 10,
+                  "core_lamb_notex": 11, "core_noorigin": 12, "core_lamb_noorigin": 13, "core_notex_noorigin": 14,
+                  "core_lamb_notex_noorigin": 15}
+
+
+def shade_steps(scene, cases, variant="shade"):
+    """Test hook (rtx_internal_shade_steps, not in rtx.h): one shading step per case
+    (SHADE_CASE_DTYPE) through the device functions the render kernels call, on the scene's own
+    material, texture and image tables; returns SHADE_RECORD_DTYPE.  variant: SHADE_VARIANTS.  A
+    "lamb" / "notex" form of a scene whose flags do not allow it raises; "terminal" marks a case
+    that does not end on the sky with cont = -1; "scatter" reads depth as the remaining depth."""
+    cases = np.ascontiguousarray(cases, dtype=SHADE_CASE_DTYPE)
+    out = np.zeros(len(cases), SHADE_RECORD_DTYPE)
+    f = lib().rtx_internal_shade_steps
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]
+    f.restype = C.c_int
+    _check(f(scene.h, cases.ctypes.data_as(C.c_void_p), len(cases), SHADE_VARIANTS[variant],
+             out.ctypes.data_as(C.c_void_p)), "rtx_internal_shade_steps")
+    return out
+
+
 def _surfels(points, normals):
     """(n, 6) doubles: point, normal (the rtx_ray layout of rtx_irradiance's surfels)."""
     points = np.asarray(points, dtype=np.float64).reshape(-1, 3)

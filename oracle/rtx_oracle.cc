@@ -147,13 +147,22 @@ inline V3 random_in_unit_disk(Rng& g) {  // math_utils.h:83-88 (y drawn before x
     if (len2(p) < 1.0) return p;
   }
 }
+// The step-level device test's libm allowance (tests/test_gpu_shade_steps.py): the cos and the
+// sin below moved by a signed number of ulps each.  0 0 (always, except in that test) is this
+// libm's cos / sin.  Set by orc_set_cos_sin_nudge.
+static int g_nudge_cos = 0, g_nudge_sin = 0;
+inline double nudge_ulps(double x, int k) {
+  for (; k > 0; k--) x = std::nextafter(x, kInf);
+  for (; k < 0; k++) x = std::nextafter(x, -kInf);
+  return x;
+}
 inline V3 random_cosine_direction(Rng& g, V3 normal) {  // math_utils.h:104-123
   double r1 = g.next();
   double r2 = g.next();
   double phi = 2.0 * kPi * r1;
   double r = std::sqrt(r2);
-  double x = r * std::cos(phi);
-  double y = r * std::sin(phi);
+  double x = r * nudge_ulps(std::cos(phi), g_nudge_cos);
+  double y = r * nudge_ulps(std::sin(phi), g_nudge_sin);
   double z = std::sqrt(1.0 - r2);
   V3 w = normalize(normal);
   V3 a = (std::fabs(w.x) > 0.9) ? v3(0, 1, 0) : v3(1, 0, 0);
@@ -1487,6 +1496,103 @@ int orc_render_samples(void* sp, orc_camera* c, const orc_params* p, double* L, 
         }
       }
     }
+  }
+  return 0;
+}
+// ---- one shading step per case (tests/test_shade_steps_host.py, tests/test_gpu_shade_steps.py) ----
+// The layouts of the device's test hook rtx_internal_shade_steps (csrc/rtx_shade_steps.h).
+struct orc_shade_case {
+  double p[3], normal[3], u, v;  // the hit record (read on a hit)
+  double o[3], d[3], thr[3];     // the path state
+  unsigned long long seed;       // the Philox key: seed, pixel, sample
+  unsigned pixel, sample;
+  int hit, front_face, mat;
+  int depth, max_depth;  // mode 1: depth is the remaining depth (GetPixel counts down from max_depth)
+  int lazy_uv;           // >= 0: u, v are this primitive's at p, as its Hit() derives them; -1: u, v above
+};
+struct orc_shade_record {
+  double L[3];                  // the radiance of a path that ended (0 0 0 of one that continues)
+  double o[3], d[3], thr[3];    // the child (all zero when the path ended)
+  double next;                  // the next draw of the segment's stream: stands for the draws consumed
+  int cont, depth;              // the child's depth (0 when the path ended)
+};
+static_assert(sizeof(orc_shade_case) == 176 && sizeof(orc_shade_record) == 112, "shade step layouts");
+
+int orc_set_cos_sin_nudge(int cos_ulps, int sin_ulps) {
+  g_nudge_cos = cos_ulps, g_nudge_sin = sin_ulps;
+  return 0;
+}
+// mode 0: the wavefront step, shade(); mode 1: the scatter-API step, one level of get_pixel: sky
+// on a miss, else mat_scatter (the child's throughput is thr * attenuation), or thr * emitted when
+// it fails.  The stream is the segment's, opened as shade() / get_pixel open it.
+int orc_shade_steps(void* sp, const orc_shade_case* cases, long long n, int mode, orc_shade_record* out) {
+  const Scene& S = *(Scene*)sp;
+  if (mode != 0 && mode != 1) {
+    g_err = "shade steps: bad mode";
+    return -1;
+  }
+  for (long long i = 0; i < n; i++) {
+    const orc_shade_case& c = cases[i];
+    if ((c.hit && (c.mat < 0 || c.mat >= (int)S.mat.size())) || c.lazy_uv < -1 || c.lazy_uv >= (int)S.prims.size() ||
+        (c.lazy_uv >= 0 && S.prims[c.lazy_uv].kind == PRIM_TRI)) {
+      g_err = "shade steps: material or primitive index out of range";
+      return -1;
+    }
+  }
+  for (long long i = 0; i < n; i++) {
+    const orc_shade_case& c = cases[i];
+    Hit rec;
+    rec.hit = c.hit != 0;
+    rec.p = v3(c.p[0], c.p[1], c.p[2]), rec.normal = v3(c.normal[0], c.normal[1], c.normal[2]);
+    rec.u = c.u, rec.v = c.v, rec.front_face = c.front_face != 0, rec.mat = c.mat;
+    if (c.lazy_uv >= 0) {
+      const Prim& P = S.prims[c.lazy_uv];
+      if (P.kind == PRIM_SPHERE) {  // hit_sphere after p
+        V3 outward = (rec.p - v3(P.g[0], P.g[1], P.g[2])) / std::fmax(0, P.g[3]);
+        rec.u = (std::atan2(-outward.z, outward.x) + kPi) / (2 * kPi);
+        rec.v = std::acos(-outward.y) / kPi;
+      } else {  // hit_rect: x, y are p's in-plane components
+        const int a0 = P.kind == PRIM_YZ ? 1 : 0, a1 = P.kind == PRIM_XY ? 1 : 2;
+        rec.u = (rec.p[a0] - P.g[0]) / (P.g[1] - P.g[0]);
+        rec.v = (rec.p[a1] - P.g[2]) / (P.g[3] - P.g[2]);
+      }
+    }
+    PathState ps;
+    ps.o = v3(c.o[0], c.o[1], c.o[2]), ps.d = v3(c.d[0], c.d[1], c.d[2]), ps.thr = v3(c.thr[0], c.thr[1], c.thr[2]);
+    ps.depth = c.depth;
+    Rng g;
+    g.mode = 1, g.seed = c.seed, g.pixel = c.pixel, g.sample = c.sample;
+    V3 L{0, 0, 0};
+    bool cont = false;
+    if (mode == 0) {
+      Params P;
+      P.max_depth = c.max_depth;
+      cont = shade(S, P, ps, rec, rec.hit, g, L);
+    } else {
+      g.open((uint32_t)(c.max_depth - c.depth) + 1u);
+      if (!rec.hit) {
+        L = ps.thr * sky(ps.d);
+      } else {
+        const Material& m = S.mat[rec.mat];
+        V3 att, so, sd;
+        if (mat_scatter(S, m, ps.d, rec, att, so, sd, g)) {
+          ps.thr = ps.thr * att, ps.o = so, ps.d = sd, ps.depth--;
+          cont = true;
+        } else {
+          L = ps.thr * mat_emitted(S, m, rec.u, rec.v, rec.p);
+        }
+      }
+    }
+    orc_shade_record r;
+    std::memset(&r, 0, sizeof r);
+    r.L[0] = L.x, r.L[1] = L.y, r.L[2] = L.z;
+    r.cont = cont;
+    if (cont) {
+      r.o[0] = ps.o.x, r.o[1] = ps.o.y, r.o[2] = ps.o.z, r.d[0] = ps.d.x, r.d[1] = ps.d.y, r.d[2] = ps.d.z;
+      r.thr[0] = ps.thr.x, r.thr[1] = ps.thr.y, r.thr[2] = ps.thr.z, r.depth = ps.depth;
+    }
+    r.next = g.next();
+    out[i] = r;
   }
   return 0;
 }

@@ -62,6 +62,9 @@ def lib():
         L.orc_philox.argtypes = [C.c_ulonglong, C.c_uint, C.c_uint, C.c_int, C.c_void_p]
         L.orc_philox_stream.argtypes = [C.c_ulonglong, C.c_uint, C.c_uint, C.c_uint, C.c_int, C.c_void_p]
         L.orc_write_ppm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p]
+        L.orc_shade_steps.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]
+        L.orc_set_cos_sin_nudge.argtypes = [C.c_int, C.c_int]
+        L.orc_set_perturb.argtypes = [C.c_int]
         _lib = L
     return _lib
 
@@ -177,6 +180,45 @@ class Scene:
         if lib().orc_render_samples(self.h, C.byref(cam), C.byref(p), _ptr(L), _ptr(segs)) != 0:
             raise RuntimeError(lib().orc_last_error().decode())
         return L, segs
+
+
+# One shading step (orc_shade_steps; the device hook rtx_internal_shade_steps has the same layouts):
+# the hit record, the path state, the Philox key, and the step's outcome.
+SHADE_CASE = np.dtype([("p", "<f8", 3), ("normal", "<f8", 3), ("u", "<f8"), ("v", "<f8"), ("o", "<f8", 3),
+                       ("d", "<f8", 3), ("thr", "<f8", 3), ("seed", "<u8"), ("pixel", "<u4"), ("sample", "<u4"),
+                       ("hit", "<i4"), ("front_face", "<i4"), ("mat", "<i4"), ("depth", "<i4"), ("max_depth", "<i4"),
+                       ("lazy_uv", "<i4")])
+SHADE_RECORD = np.dtype([("L", "<f8", 3), ("o", "<f8", 3), ("d", "<f8", 3), ("thr", "<f8", 3), ("next", "<f8"),
+                         ("cont", "<i4"), ("depth", "<i4")])
+assert SHADE_CASE.itemsize == 176 and SHADE_RECORD.itemsize == 112
+
+
+def shade_cases(n):
+    """n cases with the neutral fields set: a miss with throughput 1 1 1 and no deferred u, v."""
+    c = np.zeros(n, SHADE_CASE)
+    c["thr"], c["lazy_uv"], c["mat"] = 1.0, -1, 0
+    return c
+
+
+def shade_steps(scene, cases, scatter=False):
+    """One shading step per case on a loaded Scene: shade() (the wavefront step), or one level of
+    get_pixel (scatter=True; depth is then the remaining depth).  Returns SHADE_RECORD."""
+    cases = np.ascontiguousarray(cases, dtype=SHADE_CASE)
+    out = np.zeros(len(cases), SHADE_RECORD)
+    if lib().orc_shade_steps(scene.h, _ptr(cases), len(cases), int(scatter), _ptr(out)) != 0:
+        raise RuntimeError(lib().orc_last_error().decode())
+    return out
+
+
+def set_cos_sin_nudge(cos_ulps=0, sin_ulps=0):
+    """Moves the cos and the sin of RandomCosineDirection by a signed number of ulps each; 0 0
+    everywhere but in the step-level device test."""
+    lib().orc_set_cos_sin_nudge(int(cos_ulps), int(sin_ulps))
+
+
+def set_perturb(mode):
+    """The power checks' deliberate estimator change (orc_set_perturb); returns the previous one."""
+    return lib().orc_set_perturb(int(mode))
 
 
 def aabb(cases):
