@@ -26,8 +26,10 @@
 
 namespace rtxd {
 
-// Lambertian cos/sin: the restated small-argument forms (plain TU; with them the bunny's PARK
-// build spills, 0 -> 56 B per lane), else the library's cos() / sin()
+// Lambertian cos/sin: the restated small-argument form, cos and sin each from its own reduction
+// (plain TU, and the PARK TU's generic builds), else the library's cos() / sin() (the PARK TU's
+// Lambertian builds).  The default of cos_sin / shade_core; k_persistent picks the
+// one-shared-reduction form for its fixed-spp Lambertian texture-free PARK builds (cos_sin below)
 constexpr bool kSincosSmall = !RTX_PARK_TU;
 // kind-specialised walks: the triangle test without early exits (PARK TU: bunny +3.8 %; the
 // plain kernel's builds are slower with it)
@@ -175,9 +177,8 @@ __device__ __forceinline__ V3 random_in_unit_disk(Rng& g) {  // math_utils.h:83-
 // Lambertian angle 2*pi*r1 < 2*pi never takes, is not compiled in: its registers made the
 // shading spill.  -ffp-contract=off keeps every product and sum separately rounded, as in
 // the library; fma() is the library's fma.
-//   kSincosSmall: cos and sin each from its own small-argument reduction (fewest live
-//   registers: the plain kernel's texture-free builds lose their last spills, A/B r02
-//   `ab_sincos2_*`; one shared reduction spilled more); else the library's cos() and sin().
+// Which form a kernel takes is a matter of its register allocation alone (cos_sin below): the
+// three return the same bits.
 __device__ __forceinline__ void sincos_small(double x, double& sn, double& cs) {
   // reduction: x = q * pi/2 + (hi + lo)
   const double q = rint(x * 0x1.45f306dc9c883p-1);
@@ -217,9 +218,26 @@ __device__ __forceinline__ void sincos_small(double x, double& sn, double& cs) {
   cs = quad > 1 ? -c0 : c0;
   sn = quad > 1 ? -s0 : s0;
 }
-template <bool SMALL = kSincosSmall>
+// The three forms of the Lambertian cos/sin, equal bit for bit for 0 <= phi < 2^30
+// (tests/test_gpu_cos_sin_forms.py); register allocation decides per kernel (DESIGN.md ledger):
+//   kCosSinLib:    the library's cos() and sin(), each with its own reduction and the
+//                  large-argument path compiled in.  The PARK TU's Lambertian builds that run at
+//                  the 128-VGPR limit (the adaptive phases', the textured ones): either restated
+//                  form spills there.
+//   kCosSinEach:   sincos_small twice, cos from one reduction and sin from another (fewest live
+//                  registers across the polynomials: the plain kernel's texture-free builds lose
+//                  their last spills, A/B r02 `ab_sincos2_*`).  The plain and the queries TU, and
+//                  the PARK TU's generic builds.
+//   kCosSinShared: one sincos_small call, both values from one reduction (fewest instructions;
+//                  both polynomials' inputs are live at once).  The fixed-spp Lambertian
+//                  texture-free PARK builds, which batched shading left below the VGPR limit.
+enum CosSinForm : int { kCosSinLib = 0, kCosSinEach = 1, kCosSinShared = 2 };
+constexpr int kCosSinDefault = kSincosSmall ? kCosSinEach : kCosSinLib;
+template <int FORM = kCosSinDefault>
 __device__ __forceinline__ void cos_sin(double phi, double& c, double& s) {
-  if constexpr (SMALL) {
+  if constexpr (FORM == kCosSinShared) {
+    sincos_small(phi, s, c);
+  } else if constexpr (FORM == kCosSinEach) {
     double t;
     sincos_small(phi, t, c);
     asm volatile("" : "+v"(c));
@@ -228,6 +246,12 @@ __device__ __forceinline__ void cos_sin(double phi, double& c, double& s) {
   } else {
     c = cos(phi), s = sin(phi);
   }
+}
+// shade_core's form when its caller names none: the generic builds shade with kCosSinEach in
+// every TU, the Lambertian ones with the TU's default
+template <bool LAMB>
+constexpr int shade_cos_sin_form() {
+  return (kSincosSmall || !LAMB) ? kCosSinEach : kCosSinLib;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1440,7 +1464,9 @@ __device__ __forceinline__ V3 shade_terminal(V3 d, V3 thr) {
 // DEFER_F (texture-free builds): the BSDF value of a Lambertian / Metal hit is the material's
 // albedo (/ pi); it is read from the material table by shade_finish, at the end, instead of
 // being held in registers across the direction sampling.
-template <bool LAMB = false, bool NOTEX = false, bool SET_ORIGIN = true, bool DEFER_F = false>
+// COSSIN: the form of the Lambertian cos/sin (cos_sin above; the same bits in every form).
+template <bool LAMB = false, bool NOTEX = false, bool SET_ORIGIN = true, bool DEFER_F = false,
+          int COSSIN = shade_cos_sin_form<LAMB>()>
 __device__ __forceinline__ void shade_core(const DScene& S, int max_depth, Path& p, const Hit& rec, bool hit, Rng& g,
                                            const rtx_material& m, ShadeOut& so) {
   static_assert(!DEFER_F || NOTEX, "deferred BSDF values need texture-free shading");
@@ -1494,7 +1520,7 @@ __device__ __forceinline__ void shade_core(const DScene& S, int max_depth, Path&
   if (isL) {
     const double phi = 2.0 * kPi * r1;
     double cph, sph;
-    cos_sin<kSincosSmall || !LAMB>(phi, cph, sph);
+    cos_sin<COSSIN>(phi, cph, sph);
     x = s2 * cph;
     y = s2 * sph;
   }

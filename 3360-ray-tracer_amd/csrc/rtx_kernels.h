@@ -407,6 +407,10 @@ __global__ __launch_bounds__(kBlock, kTraceWaves) void k_persistent(RenderArgs A
   constexpr bool kBatch = kShade > 1;
   constexpr uint32_t kPendNode = 0xFFFFFFFFu;
   if (kBatch) trs.node = 0;
+  // The Lambertian cos/sin (cos_sin, rtx_device.h): the fixed-spp Lambertian texture-free PARK
+  // builds have the registers for the one-shared-reduction form; every other build keeps its
+  // TU's form (the adaptive phases' builds would reach the VGPR limit and spill with it).
+  constexpr int kCosSin = (PARK > 0 && LAMB && NOTEX && MAP == 0) ? (int)kCosSinShared : shade_cos_sin_form<LAMB>();
   // the end of a path: its radiance record
   auto end_path = [&](V3 L) {
     store_radiance(A, slot, L);
@@ -452,7 +456,7 @@ __global__ __launch_bounds__(kBlock, kTraceWaves) void k_persistent(RenderArgs A
       // across the sampling)
       ShadeOut so;
       const rtx_material& mr = *opaque(A.S.mats + (best >= 0 ? h.mat : 0));
-      shade_core<LAMB, NOTEX, !kHitpLds>(A.S, A.max_depth, P, h, best >= 0, g, mr, so);
+      shade_core<LAMB, NOTEX, !kHitpLds, false, kCosSin>(A.S, A.max_depth, P, h, best >= 0, g, mr, so);
       V3 thr = v3(thr_lds[0], thr_lds[kBlock], thr_lds[2 * kBlock]);
       cont = shade_finish(so, thr, P.depth, g, L, best >= 0 ? A.S.mats + h.mat : A.S.mats);
       if (cont) thr_lds[0] = thr.x, thr_lds[kBlock] = thr.y, thr_lds[2 * kBlock] = thr.z;
