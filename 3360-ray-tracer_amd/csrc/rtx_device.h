@@ -654,6 +654,19 @@ struct CountersClk : Counters {
   uint64_t cyc_refill, cyc_walk, cyc_shade, cyc_leaf;
   uint32_t wshade, lshade;
 };
+// The visit-order test hook's counter type (k_visit_order, rtx_park.hip): the lane's node visits
+// (the node index) and primitive tests (~primitive) in the order it makes them, with the closest
+// distance after each, the first kSeqCap of them; n counts them all.
+constexpr uint32_t kSeqCap = 64;
+struct CountersSeq : Counters {
+  int32_t* seq;
+  double* tseq;
+  uint32_t n;
+  __device__ __forceinline__ void log(int32_t what, double closest) {
+    if (n < kSeqCap) seq[n] = what, tseq[n] = closest;
+    n++;
+  }
+};
 __device__ __forceinline__ void count_prim(Counters& c, const rtx_prim* P) {
   c.prims++;
   const int k = P->kind;
@@ -915,7 +928,9 @@ __device__ __forceinline__ void trav_globals(const DScene& S, V3 o, V3 d, double
   if (S.n_global) ts.tmax_f = f32_round_up(ts.closest);
 }
 
-// Pieces of a lean BVH4 node visit shared by trace4_run and trace4_run_step.
+// Pieces of a lean BVH4 node visit shared by trace4_run and trace4_run_step (the speculative
+// walk, trace4_run_spec, has its own copy of the loads and slab arithmetic, visit_tests below: the
+// two must stay the same operations; tests/test_gpu_visit_order.py holds the copy to a restatement).
 // The slab tests of node `node`'s four slots: entry distances of the internal children entered
 // (+inf otherwise) in tt, the child words in cc; returns the mask of leaf slots entered.
 __device__ __forceinline__ uint32_t visit_slabs(const char* __restrict__ nbase, uint32_t node, const FRay4L& r,
@@ -946,6 +961,29 @@ __device__ __forceinline__ uint32_t visit_slabs(const char* __restrict__ nbase, 
     tt[c] = (hit && cc[c] >= 0) ? tn : __builtin_inff();
   }
   return lmask;
+}
+// The same loads and slab tests for a walk that does its own bookkeeping of the slots
+// (trace4_run_spec): tn the clamped entry distance of every slot, hit the slots whose box the ray
+// enters before tmax, leaf or not.  (Its own copy of the arithmetic: routing visit_slabs through
+// it changes the instruction order LLVM picks for the leaf-step kernels.)
+__device__ __forceinline__ void visit_tests(const char* __restrict__ nbase, uint32_t node, const FRay4L& r,
+                                            float tmax_x, float (&tn)[4], int32_t (&cc)[4], bool (&hit)[4]) {
+  const uint32_t noff = node << 7;
+  __builtin_amdgcn_sched_barrier(0);
+  const int4 ch = *(const int4*)(nbase + (noff + 96u));
+  const float4 ex = *(const float4*)(nbase + (noff + r.ox)), fx = *(const float4*)(nbase + (noff + (r.ox ^ 16u)));
+  const float4 ey = *(const float4*)(nbase + (noff + r.oy)), fy = *(const float4*)(nbase + (noff + (r.oy ^ 16u)));
+  const float4 ez = *(const float4*)(nbase + (noff + r.oz)), fz = *(const float4*)(nbase + (noff + (r.oz ^ 16u)));
+  __builtin_amdgcn_sched_barrier(0);
+  cc[0] = ch.x, cc[1] = ch.y, cc[2] = ch.z, cc[3] = ch.w;
+#pragma unroll
+  for (int c = 0; c < 4; c++) {
+    tn[c] = fmaxf(fmaxf(fmaf(f4c(ex, c), r.iex, r.nex), fmaf(f4c(ey, c), r.iey, r.ney)),
+                  fmaxf(fmaf(f4c(ez, c), r.iez, r.nez), 0.0f));
+    const float tf = fminf(fminf(fmaf(f4c(fx, c), r.ixx, r.nxx), fmaf(f4c(fy, c), r.ixy, r.nxy)),
+                           fminf(fmaf(f4c(fz, c), r.ixz, r.nxz), tmax_x));
+    hit[c] = tn[c] <= tf;
+  }
 }
 // The primitive of leaf slot c (its child word holds ~index)
 __device__ __forceinline__ uint32_t leaf_prim(const int32_t (&cc)[4], int c) {
@@ -1055,7 +1093,8 @@ __device__ __forceinline__ bool trace4_run_step(const DScene& S, V3 o, V3 d, dou
 constexpr uint32_t kLeafQueue = 8;
 constexpr int kLeafSpecMin = 8;
 // The lean walk with speculative node visits (Aila & Laine 2009, "speculative traversal"):
-// a visit's leaf slots go into the lane's FIFO queue (an LDS column of kLeafQueue words) and
+// a visit's leaf slots go into the lane's FIFO queue (an LDS column of kLeafQueue words, each the
+// slot's child word as the node holds it, ~primitive, complemented when it is taken out) and
 // the lane walks on; a wave runs leaf tests only when kLeafSpecMin lanes hold queued leaves,
 // or no lane can go on (each lane's queue might overflow on the next visit, its walk is over
 // or it is parking), and then every lane with a queued leaf tests one; a lane that cannot
@@ -1098,19 +1137,31 @@ __device__ __forceinline__ bool trace4_run_spec(const DScene& S, V3 o, V3 d, dou
         cnt.nodes++;
         if (first_active_lane()) cnt.wnodes++;
       }
-      uint32_t lmask = visit_slabs(nbase, node, r, tmax_x, tt, cc);
-      while (lmask) {
-        lq[((qh + qn) & (F - 1)) * stride] = leaf_prim(cc, __builtin_ctz(lmask));
-        lmask &= lmask - 1u;
-        qn++;
+      if constexpr (std::is_same_v<CNT, CountersSeq>) cnt.log((int32_t)node, closest);
+      // The leaf slots entered go into the queue in slot order, without a loop over a leaf
+      // mask: every slot's child word is stored at the tail, and the tail moves on only past a
+      // leaf slot that was entered (the next store overwrites any other).  A visit starts with
+      // at most F - 4 words queued, so the four stores stay clear of the words still waiting.
+      // The queue holds child words as the node has them (~primitive).
+      float tn[4];
+      bool hit[4];
+      visit_tests(nbase, node, r, tmax_x, tn, cc, hit);
+      uint32_t qt = qh + qn;
+#pragma unroll
+      for (int c = 0; c < 4; c++) {
+        const bool leaf = cc[c] < 0;
+        lq[(qt & (F - 1)) * stride] = (uint32_t)cc[c];
+        qt += (uint32_t)(hit[c] & leaf);
+        tt[c] = (hit[c] & !leaf) ? tn[c] : __builtin_inff();
       }
+      qn = qt - qh;
       walking = visit_next<STACK, uint16_t>(tt, cc, false, closest, tmax_f, tmax_x, stk, stride, sp, node);
     }
     const bool can_visit = walking && !park && qn <= F - 4;
     if (__ballot(can_visit) == 0 || __popcll(__ballot(qn != 0)) >= kLeafSpecMin) {
       if constexpr (std::is_same_v<CNT, CountersClk>) cnt.t_leaf = __builtin_amdgcn_s_memtime();
       if (qn != 0) {  // one queued leaf, in visit order
-        const uint32_t cur = lq[qh * stride];
+        const uint32_t cur = ~lq[qh * stride];
         qh = (qh + 1) & (F - 1), qn--;
         if (COUNT) {
           count_prim(cnt, S.prims + cur);
@@ -1121,6 +1172,7 @@ __device__ __forceinline__ bool trace4_run_spec(const DScene& S, V3 o, V3 d, dou
           tmax_f = f32_round_up(closest);
           tmax_x = tmax_f * 1.00001f;
         }
+        if constexpr (std::is_same_v<CNT, CountersSeq>) cnt.log(~(int32_t)cur, closest);
       }
       if constexpr (std::is_same_v<CNT, CountersClk>)
         if (first_active_lane()) cnt.cyc_leaf += __builtin_amdgcn_s_memtime() - cnt.t_leaf;
