@@ -623,10 +623,16 @@ int set_segbuf(unsigned long long* ctr, uint16_t* segs, hipStream_t st) {
 // or stop; every phase is a launch of its own with its own drain.
 // `mark` records a hot-kernel timing event (before and after each persistent launch);
 // hot_launches counts them.  The caller resolves the pixels (k_resolve).
-template <class Mark, class Early>
+// `trace(g, Lg, Ag, ctr, nslots)` fills phase g's nslots radiance records (Ag.L; slot p * Ag.K + k
+// in phase 1, the slot map's (pixel, sample) afterwards): the persistent launch (trace_persistent)
+// in renders, a gather from a caller's table in the test hook rtx_internal_adaptive_replay.
+inline int trace_persistent(int, const Launch& Lg, const RenderArgs& Ag, unsigned long long* ctr, uint64_t) {
+  return persist_m<false>(Lg, Ag, ctr);
+}
+template <class Mark, class Early, class Trace>
 int render_adaptive(rtx_scene* sc, const Launch& L, const RenderArgs& A, const rtx_render_params* prm,
                     const PixelSoA& px, int budget, double other, hipStream_t s, Mark mark, uint64_t& hot_launches,
-                    Early early) {
+                    Early early, Trace trace) {
   const int64_t npix = A.npix;
   const int K1 = std::min(std::max(1, prm->min_spp), budget);
   static const bool debug = std::getenv("RTX_DEBUG_ADAPT") != nullptr;  // per-phase slot counts on stderr
@@ -706,7 +712,7 @@ int render_adaptive(rtx_scene* sc, const Launch& L, const RenderArgs& A, const r
   };
   // one persistent launch of a phase; debug: its time and segments on stderr
   // uniform: the launch's slot count (no slot map: uniform groups); 0: the slot map's, from k_adapt_expand
-  auto launch = [&](int g, const Launch& Lg, const RenderArgs& Ag, uint16_t* segs, int64_t pixels,
+  auto launch = [&](int g, const Launch& Lg, const RenderArgs& Ag, uint16_t* segs, int64_t pixels, uint64_t nslots,
                     uint64_t uniform = 0) -> int {
     unsigned long long seg0 = 0;
     hipLaunchKernelGGL(k_slot_block_init, dim3(1), dim3(8 * 16), 0, s, ctr, uniform ? 1 : 0,
@@ -721,7 +727,7 @@ int render_adaptive(rtx_scene* sc, const Launch& L, const RenderArgs& A, const r
     if (debug) HIPC(hipMemsetAsync(A.counters + 13, 0, 5 * sizeof(unsigned long long), s));  // (the timeline)
     if ((rc2 = mark(s))) return rc2;
     if (L.count && (rc2 = set_segbuf(ctr, segs, s))) return rc2;
-    if ((rc2 = persist_m<false>(Lg, Ag, ctr))) return rc2;
+    if ((rc2 = trace(g, Lg, Ag, ctr, nslots))) return rc2;
     L.build = Lg.build;  // (the stats report the instantiation launched last)
     if ((rc2 = mark(s))) return rc2;
     hot_launches++;
@@ -758,8 +764,8 @@ int render_adaptive(rtx_scene* sc, const Launch& L, const RenderArgs& A, const r
   Launch L1 = L;
   const bool first_map1 = (g_tune.first_map >= 0 ? g_tune.first_map : kFirstPassMap) == 1;
   if (first_map1) L1.map = 1;
-  if ((rc = launch(1, L1, A1, sc->segs1.as<uint16_t>(), npix, first_map1 ? (uint64_t)npix * (uint64_t)K1 : 0)))
-    return rc;
+  const uint64_t nslots1 = (uint64_t)npix * (uint64_t)K1;
+  if ((rc = launch(1, L1, A1, sc->segs1.as<uint16_t>(), npix, nslots1, first_map1 ? nslots1 : 0))) return rc;
   if ((rc = record(1, sc->lbuf.as<double>(), npix))) return rc;
   RenderArgs Ag = A;
   Ag.L = w.lbuf.as<double>();
@@ -776,9 +782,61 @@ int render_adaptive(rtx_scene* sc, const Launch& L, const RenderArgs& A, const r
     // the output once few pixels are left: every other pixel is final (phase g's list holds the
     // rest, and later phases' lists are subsets of it)
     if ((rc = early(g, active, w.lst[g & 1].as<uint32_t>()))) return rc;
-    if ((rc = launch(g, Lg, Ag, w.segs.as<uint16_t>(), active))) return rc;
+    if ((rc = launch(g, Lg, Ag, w.segs.as<uint16_t>(), active, nsl))) return rc;
     if ((rc = record(g, Ag.L, active))) return rc;
   }
+  return RTX_OK;
+}
+
+// How one uniform group of radiance records (L: npix x K records, pixel-major) enters the pixel
+// statistics: render_device_impl's launches after each group, shared with the test hook
+// rtx_internal_accumulate_groups.
+//   kAccRecord      RecordSample + IsConverged in sample order (k_accumulate; adaptive 0: no test)
+//   kAccSum         fixed spp (RecordSample's in-order sum, or the megakernel's DefaultSampler):
+//                   only sum / (float)samples reaches the output, and the in-order sum is the
+//                   same as RecordSample's; the Welford mean / M2 (three divisions per sample)
+//                   only feed IsConverged, which adaptive sampling alone consults.  `first`: the
+//                   group starts the sums; out.resolve >= 0 (the last group): the resolved output
+//                   instead of the running sums, in `bands` bands of the pixels whose edges are
+//                   multiples of `align` (after_band(b, q0, q1) follows each band's launch)
+//   kAccMkAdaptive  the megakernel's AdaptiveSampler(min_spp, spp, rel)
+enum AccKind { kAccRecord = 0, kAccSum = 1, kAccMkAdaptive = 2 };
+struct GroupAcc {
+  AccKind kind;
+  int adaptive, min_spp, spp;
+  double rel;
+  bool first = false;
+  AccOut out{nullptr, nullptr, -1, 0};
+  int bands = 1;
+  int64_t align = 1;
+};
+template <class AfterBand>
+int accumulate_group(hipStream_t s, const PixelSoA& px, const double* L, int64_t npix, int K, const GroupAcc& ga,
+                     AfterBand after_band) {
+  const int pix_blocks = (int)((npix + kBlock - 1) / kBlock);
+  if (ga.kind == kAccMkAdaptive)
+    hipLaunchKernelGGL(k_accumulate_mk_adaptive, dim3(pix_blocks), dim3(kBlock), 0, s, px, L, npix, K, ga.min_spp,
+                       ga.spp, ga.rel);
+  else if (ga.kind == kAccSum) {
+    AccOut out = ga.out;
+    out.spp = ga.spp;
+    const int nb = std::max(1, ga.bands);
+    const int64_t align = std::max<int64_t>(1, ga.align);
+    const int64_t units = (npix + align - 1) / align;
+    int rc;
+    for (int b = 0; b < nb; b++) {
+      const int64_t q0 = std::min<int64_t>(npix, units * b / nb * align);
+      const int64_t q1 = std::min<int64_t>(npix, units * (b + 1) / nb * align);
+      if (q1 <= q0) continue;
+      hipLaunchKernelGGL(k_accumulate_sum, dim3((unsigned)((q1 - q0 + kAccPix - 1) / kAccPix)), dim3(kAccWave), 0, s,
+                         px, L, npix, K, q0, q1, ga.first ? 1 : 0, out);
+      HIPC(hipGetLastError());
+      if ((rc = after_band(b, q0, q1))) return rc;
+    }
+  } else
+    hipLaunchKernelGGL(k_accumulate, dim3(pix_blocks), dim3(kBlock), 0, s, px, L, npix, K, ga.adaptive, ga.min_spp,
+                       ga.rel);
+  HIPC(hipGetLastError());
   return RTX_OK;
 }
 
@@ -1433,7 +1491,7 @@ static int render_device_impl(rtx_scene* sc, const rtx_camera* cam, const rtx_re
              HIPC(hipEventRecord(e, st));
            }
            return RTX_OK;
-         }, hot_launches, early))) {
+         }, hot_launches, early, trace_persistent))) {
       // an error after the early output was queued: the copy into the caller's framebuffer
       // must be over before the caller gets the error (and may free or reuse the buffer)
       if (patch_n >= 0) (void)hipEventSynchronize(sc->band_ev[1]);
@@ -1494,38 +1552,22 @@ static int render_device_impl(rtx_scene* sc, const rtx_camera* cam, const rtx_re
       if ((rc = hot_begin())) return rc;
       hot_launches++;
     }
-    if (mk_adaptive)
-      hipLaunchKernelGGL(k_accumulate_mk_adaptive, dim3(pix_blocks), dim3(kBlock), 0, s, px, A.L, npix, Kc,
-                         prm->min_spp, prm->spp, prm->rel_threshold);
-    else if (sum_path) {
-      // fixed spp: only sum/(float)samples reaches the output, and the in-order sum is the
-      // same as RecordSample's; the Welford mean/M2 (three divisions per sample) only feed
-      // IsConverged, which adaptive sampling alone consults.  The last group writes the
-      // resolved output itself (k_resolve's arithmetic), in bands when a sink takes them.
-      const bool last = s0 + Kc >= budget;
-      AccOut out{nullptr, nullptr, -1, prm->spp};
-      if (last && !film) out = AccOut{d_rgb, d_spp, prm->mode == RTX_MODE_MEGAKERNEL ? 1 : 0, prm->spp};
-      const int nb = (last && banded) ? kBands : 1;
-      const int64_t align = banded ? std::max<int64_t>(1, sink->align) : 1;
-      const int64_t units = (npix + align - 1) / align;
-      for (int b = 0; b < nb; b++) {
-        const int64_t q0 = std::min<int64_t>(npix, units * b / nb * align);
-        const int64_t q1 = std::min<int64_t>(npix, units * (b + 1) / nb * align);
-        if (q1 <= q0) continue;
-        hipLaunchKernelGGL(k_accumulate_sum, dim3((unsigned)((q1 - q0 + kAccPix - 1) / kAccPix)), dim3(kAccWave), 0,
-                           s, px, A.L, npix, Kc, q0, q1, s0 == 0 ? 1 : 0, out);
-        HIPC(hipGetLastError());
-        if (last && banded) {
-          HIPC(hipEventRecord(sc->band_ev[b], s));
-          HIPC(hipStreamWaitEvent(sc->copy_stream, sc->band_ev[b], 0));
-          if ((rc = sink->copy(sink->ctx, q0, q1, sc->copy_stream))) return rc;
-        }
-      }
-      resolved = last;
-    } else
-      hipLaunchKernelGGL(k_accumulate, dim3(pix_blocks), dim3(kBlock), 0, s, px, A.L, npix, Kc, prm->adaptive,
-                         prm->min_spp, prm->rel_threshold);
-    HIPC(hipGetLastError());
+    // fixed spp: the last group writes the resolved output itself (k_resolve's arithmetic), in
+    // bands when a sink takes them
+    const bool last = s0 + Kc >= budget;
+    GroupAcc ga{mk_adaptive ? kAccMkAdaptive : sum_path ? kAccSum : kAccRecord, prm->adaptive, prm->min_spp, prm->spp,
+                prm->rel_threshold};
+    ga.first = s0 == 0;
+    if (sum_path && last && !film) ga.out = AccOut{d_rgb, d_spp, prm->mode == RTX_MODE_MEGAKERNEL ? 1 : 0, prm->spp};
+    if (sum_path && last && banded) ga.bands = kBands, ga.align = std::max<int64_t>(1, sink->align);
+    if ((rc = accumulate_group(s, px, A.L, npix, Kc, ga, [&](int b, int64_t q0, int64_t q1) -> int {
+           if (!(sum_path && last && banded)) return RTX_OK;
+           HIPC(hipEventRecord(sc->band_ev[b], s));
+           HIPC(hipStreamWaitEvent(sc->copy_stream, sc->band_ev[b], 0));
+           return sink->copy(sink->ctx, q0, q1, sc->copy_stream);
+         })))
+      return rc;
+    if (sum_path) resolved = last;
   }
   if (!resolved && !film) {
     hipLaunchKernelGGL(k_resolve, dim3(pix_blocks), dim3(kBlock), 0, s, px, npix,
@@ -2336,6 +2378,192 @@ extern "C" int rtx_internal_adapt_tune(int64_t phase_slots, int32_t phase_kcap, 
                                        double margin1, double pool_w) {
   if (phase_slots < 0 || phase_kcap < 0 || first_map > 1) return fail(RTX_ERR_INVALID, "bad tuning value");
   g_tune = AdaptTune{phase_slots, phase_kcap, first_map, phase_mstep, margin1, pool_w};
+  return RTX_OK;
+}
+
+namespace {
+struct TmpBuf : DevBuf {  // a hook's own device buffer, freed when the hook returns
+  ~TmpBuf() { release(); }
+};
+// the pixel statistics (channel-major on the device) to the caller's [npix][3] / [npix] arrays
+int read_pixels(const PixelSoA& px, int64_t npix, double* sum, double* mean, double* m2, int32_t* samples,
+                uint8_t* conv) {
+  std::vector<double> h(3 * (size_t)npix);
+  const double* src[3] = {px.sum, px.mean, px.m2};
+  double* dst[3] = {sum, mean, m2};
+  for (int a = 0; a < 3; a++) {
+    if (!dst[a]) continue;
+    HIPC(hipMemcpy(h.data(), src[a], h.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int64_t p = 0; p < npix; p++)
+      for (int c = 0; c < 3; c++) dst[a][3 * p + c] = h[(size_t)c * npix + p];
+  }
+  if (samples) HIPC(hipMemcpy(samples, px.samples, npix * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (conv) HIPC(hipMemcpy(conv, px.conv, npix, hipMemcpyDeviceToHost));
+  return RTX_OK;
+}
+}  // namespace
+
+// Test hook (not in rtx.h): render_adaptive's own phase loop (record, plan, floor, scan, expand,
+// the host's read of the slot and pixel counts, the workspace sizing; rtx_internal_adapt_tune
+// applies) on a caller's table of radiance samples, table[p][k] (3 doubles) being sample k of
+// pixel p, k < budget: each phase's persistent launch is replaced by a gather of the phase's
+// slots from the table (k_gather_table).  The pixels form a grid `width` columns wide
+// (k_adapt_plan's neighbourhoods).  Out: the pixel statistics ([npix][3] doubles, samples,
+// conv), k_resolve's output (rgb, spp_out), and asked[p * budget + k], how often the phases asked
+// for each (pixel, sample), saturated at 255.
+extern "C" int rtx_internal_adaptive_replay(rtx_scene* sc, const double* table, int64_t npix, int32_t width,
+                                            int32_t budget, int32_t min_spp, double rel, double* sum, double* mean,
+                                            double* m2, int32_t* samples, uint8_t* conv, double* rgb, int32_t* spp_out,
+                                            uint8_t* asked) {
+  if (!sc || !table || !rgb || !asked) return fail(RTX_ERR_INVALID, "NULL argument");
+  if (npix < 1 || width < 1 || budget < 1 || npix * (int64_t)budget > (1ll << 24))
+    return fail(RTX_ERR_INVALID, "adaptive replay: bad table size");
+  HIPC(hipSetDevice(sc->device));
+  hipStream_t s = sc->stream;
+  const size_t entries = (size_t)npix * budget;
+  TmpBuf d_table, d_asked, d_bad, d_rgb, d_spp;
+  int rc;
+  if ((rc = d_table.reserve(entries * 3 * sizeof(double)))) return rc;
+  if ((rc = d_asked.reserve(entries * sizeof(uint32_t)))) return rc;
+  if ((rc = d_bad.reserve(sizeof(unsigned long long)))) return rc;
+  if ((rc = d_rgb.reserve(npix * 3 * sizeof(double)))) return rc;
+  if ((rc = d_spp.reserve(npix * sizeof(int32_t)))) return rc;
+  HIPC(hipMemcpy(d_table.p, table, entries * 3 * sizeof(double), hipMemcpyHostToDevice));
+  HIPC(hipMemset(d_asked.p, 0, entries * sizeof(uint32_t)));
+  HIPC(hipMemset(d_bad.p, 0, sizeof(unsigned long long)));
+  if ((rc = sc->px_sum.reserve(npix * 3 * sizeof(double)))) return rc;
+  if ((rc = sc->px_mean.reserve(npix * 3 * sizeof(double)))) return rc;
+  if ((rc = sc->px_m2.reserve(npix * 3 * sizeof(double)))) return rc;
+  if ((rc = sc->px_samples.reserve(npix * sizeof(int32_t)))) return rc;
+  if ((rc = sc->px_conv.reserve(npix))) return rc;
+  if ((rc = sc->counters.reserve(kCounterWords * sizeof(unsigned long long)))) return rc;
+  const PixelSoA px{sc->px_sum.as<double>(), sc->px_mean.as<double>(), sc->px_m2.as<double>(),
+                    sc->px_samples.as<int32_t>(), sc->px_conv.as<uint8_t>()};
+  {
+    const int64_t n = std::max<int64_t>(npix, kCounterWords);
+    hipLaunchKernelGGL(k_frame_init, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, px, npix, 1,
+                       sc->counters.as<unsigned long long>(), kCounterWords);
+    HIPC(hipGetLastError());
+  }
+  rtx_render_params prm{};
+  prm.spp = budget, prm.adaptive = 1, prm.min_spp = min_spp, prm.rel_threshold = rel;
+  prm.mode = RTX_MODE_PERSISTENT;
+  RenderArgs A{};
+  A.S = sc->S;
+  A.npix = npix;
+  A.map = PixelMap{};
+  A.map.W = A.map.w = width;
+  A.map.H = A.map.h = (int32_t)((npix + width - 1) / width);
+  set_map_div(A.map);
+  A.conv = px.conv;
+  A.L = sc->lbuf.as<double>();
+  A.counters = sc->counters.as<unsigned long long>();
+  Launch L{sc, s, sc->stack_parity, false, false};
+  uint64_t hot_launches = 0;
+  rc = render_adaptive(
+      sc, L, A, &prm, px, budget, 0.0, s, [](hipStream_t) -> int { return RTX_OK; }, hot_launches,
+      [](int, int64_t, const uint32_t*) -> int { return RTX_OK; },
+      [&](int g, const Launch&, const RenderArgs& Ag, unsigned long long*, uint64_t nslots) -> int {
+        if (nslots == 0) return RTX_OK;
+        hipLaunchKernelGGL(k_gather_table, dim3((unsigned)((nslots + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
+                           d_table.as<double>(), npix, budget, Ag.L, nslots, g == 1 ? (uint32_t)Ag.K : 0u,
+                           sc->aw.smap.as<uint2>(), d_asked.as<uint32_t>(), d_bad.as<unsigned long long>());
+        HIPC(hipGetLastError());
+        return RTX_OK;
+      });
+  if (rc) {
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  hipLaunchKernelGGL(k_resolve, dim3((unsigned)((npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, px, npix, 0, budget,
+                     d_rgb.as<double>(), d_spp.as<int32_t>());
+  HIPC(hipGetLastError());
+  HIPC(hipStreamSynchronize(s));
+  unsigned long long bad = 0;
+  HIPC(hipMemcpy(&bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost));
+  if (bad) return fail(RTX_ERR_INVALID, "adaptive replay: " + std::to_string(bad) + " slots outside the table");
+  if ((rc = read_pixels(px, npix, sum, mean, m2, samples, conv))) return rc;
+  HIPC(hipMemcpy(rgb, d_rgb.p, npix * 3 * sizeof(double), hipMemcpyDeviceToHost));
+  if (spp_out) HIPC(hipMemcpy(spp_out, d_spp.p, npix * sizeof(int32_t), hipMemcpyDeviceToHost));
+  std::vector<uint32_t> h(entries);
+  HIPC(hipMemcpy(h.data(), d_asked.p, entries * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < entries; i++) asked[i] = (uint8_t)std::min<uint32_t>(h[i], 255u);
+  return RTX_OK;
+}
+
+// Test hook (not in rtx.h): a caller's table of radiance samples (table[p][k], 3 doubles, k <
+// budget) fed in uniform groups of groups[0], groups[1], ... samples (they sum to the budget)
+// through render_device_impl's own accumulate launches (accumulate_group), then resolved.
+//   kind 0 / 1  k_accumulate, adaptive on / off (min_spp, rel), then k_resolve
+//   kind 2      k_accumulate_sum: the first group with `first`, running sums after it; resolve -1:
+//               k_resolve after the last group, 0 / 1: the last group writes the resolved pixel
+//               (sum / (float)samples, or the DefaultSampler's sum / spp) in `bands` bands whose
+//               edges are multiples of `align` pixels.  The sums start from NaN: `first` must not
+//               read them
+//   kind 3      k_accumulate_mk_adaptive: AdaptiveSampler(min_spp, budget - 1, rel), then k_resolve
+// Out: the pixel statistics as the kernels left them ([npix][3] doubles, samples, conv) and the
+// resolved output (rgb, spp_out).
+extern "C" int rtx_internal_accumulate_groups(int device, int32_t kind, const double* table, int64_t npix,
+                                              int32_t budget, const int32_t* groups, int32_t n_groups, int32_t bands,
+                                              int64_t align, int32_t min_spp, double rel, int32_t resolve,
+                                              double* sum, double* mean, double* m2, int32_t* samples, uint8_t* conv,
+                                              double* rgb, int32_t* spp_out) {
+  if (!table || !groups || !rgb) return fail(RTX_ERR_INVALID, "NULL argument");
+  if (kind < 0 || kind > 3 || npix < 1 || budget < 1 || n_groups < 1 || bands < 1 || align < 1 || resolve < -1 ||
+      resolve > 1 || npix * (int64_t)budget > (1ll << 24))
+    return fail(RTX_ERR_INVALID, "accumulate groups: bad arguments");
+  int64_t total = 0;
+  int kmax = 0;
+  for (int i = 0; i < n_groups; i++) {
+    if (groups[i] < 1) return fail(RTX_ERR_INVALID, "accumulate groups: empty group");
+    total += groups[i], kmax = std::max(kmax, groups[i]);
+  }
+  if (total != budget) return fail(RTX_ERR_INVALID, "accumulate groups: the groups do not sum to the budget");
+  HIPC(hipSetDevice(device));
+  TmpBuf b_sum, b_mean, b_m2, b_samples, b_conv, b_L, b_rgb, b_spp;
+  int rc;
+  for (TmpBuf* b : {&b_sum, &b_mean, &b_m2, &b_rgb})
+    if ((rc = b->reserve(npix * 3 * sizeof(double)))) return rc;
+  if ((rc = b_samples.reserve(npix * sizeof(int32_t))) || (rc = b_spp.reserve(npix * sizeof(int32_t)))) return rc;
+  if ((rc = b_conv.reserve(npix)) || (rc = b_L.reserve((size_t)npix * kmax * 3 * sizeof(double)))) return rc;
+  const int fill = kind == 2 ? 0xFF : 0;  // (0xFF bytes: NaN sums, count -1, which `first` must not read)
+  for (TmpBuf* b : {&b_sum, &b_mean, &b_m2, &b_samples}) HIPC(hipMemset(b->p, fill, b->n));
+  HIPC(hipMemset(b_conv.p, 0, b_conv.n));
+  HIPC(hipMemset(b_rgb.p, 0xFF, b_rgb.n));
+  HIPC(hipMemset(b_spp.p, 0xFF, b_spp.n));
+  const PixelSoA px{b_sum.as<double>(), b_mean.as<double>(), b_m2.as<double>(), b_samples.as<int32_t>(),
+                    b_conv.as<uint8_t>()};
+  hipStream_t s = nullptr;
+  std::vector<double> h;
+  bool resolved = false;
+  for (int i = 0, s0 = 0; i < n_groups; s0 += groups[i], i++) {
+    const int K = groups[i];
+    h.resize((size_t)npix * K * 3);
+    for (int64_t p = 0; p < npix; p++)
+      std::memcpy(h.data() + (size_t)p * K * 3, table + ((size_t)p * budget + s0) * 3, (size_t)K * 3 * sizeof(double));
+    HIPC(hipMemcpy(b_L.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+    const bool last = i == n_groups - 1;
+    GroupAcc ga{kind == 3 ? kAccMkAdaptive : kind == 2 ? kAccSum : kAccRecord, kind == 0 ? 1 : 0, min_spp,
+                kind == 3 ? budget - 1 : budget, rel};
+    ga.first = s0 == 0;
+    if (kind == 2 && last && resolve >= 0) {
+      ga.out = AccOut{b_rgb.as<double>(), b_spp.as<int32_t>(), resolve, budget};
+      ga.bands = bands, ga.align = align;
+      resolved = true;
+    }
+    if ((rc = accumulate_group(s, px, b_L.as<double>(), npix, K, ga, [](int, int64_t, int64_t) -> int { return RTX_OK; })))
+      return rc;
+    HIPC(hipStreamSynchronize(s));  // (b_L is rewritten for the next group)
+  }
+  if (!resolved) {
+    hipLaunchKernelGGL(k_resolve, dim3((unsigned)((npix + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, px, npix,
+                       kind == 3 ? 2 : 0, budget, b_rgb.as<double>(), b_spp.as<int32_t>());
+    HIPC(hipGetLastError());
+    HIPC(hipStreamSynchronize(s));
+  }
+  if ((rc = read_pixels(px, npix, sum, mean, m2, samples, conv))) return rc;
+  HIPC(hipMemcpy(rgb, b_rgb.p, npix * 3 * sizeof(double), hipMemcpyDeviceToHost));
+  if (spp_out) HIPC(hipMemcpy(spp_out, b_spp.p, npix * sizeof(int32_t), hipMemcpyDeviceToHost));
   return RTX_OK;
 }
 

@@ -126,7 +126,8 @@ __device__ __forceinline__ void record_update(PixRec& r, const double (&x)[3]) {
 // err / mu > rel  <=>  m2 > rel^2 (n - 1) n mu^2 up to the few ulps the exact form rounds by,
 // so the products decide where the two sides differ by more than 1e-10 relative (the usual
 // case), the exact form (two divisions, two square roots) only in between; NaN fails both
-// comparisons and takes the exact form too.  (All channels must pass: a conjunction, so the
+// comparisons and takes the exact form too, and so does a rel that is not >= 0 (the products
+// only stand for the quotient when rel is not negative).  (All channels must pass: a conjunction, so the
 // order of the reference's early exit does not matter.)
 __device__ __forceinline__ bool record_converged(const PixRec& r, int min_spp, double rel) {
   if (r.n < min_spp) return false;
@@ -135,8 +136,10 @@ __device__ __forceinline__ bool record_converged(const PixRec& r, int min_spp, d
   for (int c = 0; c < 3; c++) {
     const double mu = fmax(fabs(r.mean[c]), 1e-3);
     const double thr = rel * rel * ((double)(r.n - 1) * (double)r.n * (mu * mu));
-    if (r.m2[c] > thr * (1.0 + 1e-10)) ok = false;
-    else if (__builtin_expect(!(r.m2[c] < thr * (1.0 - 1e-10)), 0)) {
+    // (rel < 0 or NaN: rel * rel would stand for |rel|, while err / mu > rel holds for every finite
+    // pixel when rel < 0, so such a rel takes the exact form)
+    if (rel >= 0.0 && r.m2[c] > thr * (1.0 + 1e-10)) ok = false;
+    else if (__builtin_expect(!(rel >= 0.0 && r.m2[c] < thr * (1.0 - 1e-10)), 0)) {
       double var = r.n > 1 ? r.m2[c] / (r.n - 1) : 0.0;
       double err = sqrt(var) / sqrt((double)r.n);
       if (err / mu > rel) ok = false;
@@ -699,6 +702,32 @@ __global__ __launch_bounds__(kBlock) void k_camera_rays(rtx_camera cam, PixelMap
   get_ray(cam, x, y, g, o, d);
   double* q = out + 6 * (uint64_t)j;
   q[0] = o.x, q[1] = o.y, q[2] = o.z, q[3] = d.x, q[4] = d.y, q[5] = d.z;
+}
+
+// Test hook (rtx_internal_adaptive_replay): an adaptive phase's radiance records gathered from a
+// caller's table [npix][budget][3] instead of traced.  Slot j holds sample k of pixel p: kuni > 0
+// (the uniform first phase) p = j / kuni, k = j % kuni, else smap[j] (k_adapt_expand's slot map).
+// asked[p * budget + k] counts the requests for each (pixel, sample); a slot
+// outside the table gets NaN and is counted in *bad (nothing outside the table is touched).
+__global__ __launch_bounds__(kBlock) void k_gather_table(const double* __restrict__ table, int64_t npix, int budget,
+                                                         double* __restrict__ L, uint64_t nslots, uint32_t kuni,
+                                                         const uint2* __restrict__ smap, uint32_t* __restrict__ asked,
+                                                         unsigned long long* __restrict__ bad) {
+  const uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (j >= nslots) return;
+  uint32_t p, k;
+  if (kuni) p = (uint32_t)(j / kuni), k = (uint32_t)(j - (uint64_t)p * kuni);
+  else p = smap[j].x, k = smap[j].y;
+  double* o = L + 3 * j;
+  if ((int64_t)p >= npix || k >= (uint32_t)budget) {
+    o[0] = o[1] = o[2] = __builtin_nan("");
+    atomicAdd(bad, 1ull);
+    return;
+  }
+  const int64_t e = (int64_t)p * budget + k;
+  const double* x = table + 3 * e;
+  o[0] = x[0], o[1] = x[1], o[2] = x[2];
+  atomicAdd(asked + e, 1u);
 }
 
 }  // namespace rtxd

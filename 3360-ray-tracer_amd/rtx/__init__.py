@@ -895,6 +895,55 @@ def adapt_tune(phase_slots=0, phase_kcap=0, first_map=-1, phase_mstep=-1.0, marg
     _check(f(phase_slots, phase_kcap, first_map, phase_mstep, margin1, pool_w), "rtx_internal_adapt_tune")
 
 
+def _pixel_outputs(npix):
+    r = {k: np.zeros((npix, 3)) for k in ("sum", "mean", "m2", "rgb")}
+    r["samples"], r["conv"], r["spp"] = np.zeros(npix, np.int32), np.zeros(npix, np.uint8), np.zeros(npix, np.int32)
+    return r, [r[k].ctypes.data_as(C.c_void_p) for k in ("sum", "mean", "m2", "samples", "conv", "rgb", "spp")]
+
+
+def adaptive_replay(scene, table, width, min_spp, rel):
+    """Test hook (rtx_internal_adaptive_replay, not in rtx.h): the adaptive persistent render's own
+    phase loop on a table of radiance samples [npix, budget, 3] instead of traced paths, the
+    pixels a grid `width` columns wide (adapt_tune applies).  Returns the pixel statistics (sum,
+    mean, m2 [npix, 3], samples, conv), k_resolve's output (rgb, spp) and asked [npix, budget]
+    (uint8): how often the phases asked for each (pixel, sample)."""
+    table = np.ascontiguousarray(table, dtype=np.float64)
+    npix, budget = table.shape[:2]
+    assert table.shape == (npix, budget, 3)
+    r, ptrs = _pixel_outputs(npix)
+    r["asked"] = np.zeros((npix, budget), np.uint8)
+    f = lib().rtx_internal_adaptive_replay
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_double] + [C.c_void_p] * 8
+    f.restype = C.c_int
+    _check(f(scene.h, table.ctypes.data_as(C.c_void_p), npix, width, budget, min_spp, float(rel), *ptrs,
+             r["asked"].ctypes.data_as(C.c_void_p)), "rtx_internal_adaptive_replay")
+    return r
+
+
+ACC_KINDS = {"record_adaptive": 0, "record": 1, "sum": 2, "mk_adaptive": 3}
+
+
+def accumulate_groups(kind, table, groups, min_spp=16, rel=0.05, resolve=-1, bands=1, align=1, device=0):
+    """Test hook (rtx_internal_accumulate_groups, not in rtx.h): a table of radiance samples [npix,
+    budget, 3] fed in uniform groups of groups[i] samples through the renderer's own accumulate
+    launches: "record_adaptive" / "record" k_accumulate with adaptive on / off, "sum"
+    k_accumulate_sum (resolve -1: k_resolve afterwards; 0 / 1: the last group resolves, in `bands`
+    bands aligned to `align` pixels), "mk_adaptive" AdaptiveSampler(min_spp, budget - 1, rel).
+    Returns the pixel statistics as the kernels left them and the resolved output (rgb, spp)."""
+    table = np.ascontiguousarray(table, dtype=np.float64)
+    npix, budget = table.shape[:2]
+    assert table.shape == (npix, budget, 3)
+    g = np.ascontiguousarray(groups, dtype=np.int32)
+    r, ptrs = _pixel_outputs(npix)
+    f = lib().rtx_internal_accumulate_groups
+    f.argtypes = [C.c_int, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
+                  C.c_int32, C.c_double, C.c_int32] + [C.c_void_p] * 7
+    f.restype = C.c_int
+    _check(f(device, ACC_KINDS[kind], table.ctypes.data_as(C.c_void_p), npix, budget, g.ctypes.data_as(C.c_void_p),
+             len(g), bands, align, min_spp, float(rel), resolve, *ptrs), "rtx_internal_accumulate_groups")
+    return r
+
+
 def early_output_stats():
     """Test hook (rtx_internal_early_output_stats, not in rtx.h): (adaptive renders of this
     process whose output went to the host while phases still ran, pixels the device patched

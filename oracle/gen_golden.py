@@ -13,6 +13,8 @@ and writes small fixtures (inputs + expected outputs) under tests/golden/:
   hits_<scene>.npz       rays + closest-hit records via CPURayIntegrator::IntersectBatch
   aabb.npz               Aabb::Hit cases incl. axis-parallel / NaN rays
   material.npz, scatter.npz, texture.npz, pixelstate.npz
+  pixelstate_edges.npz   RecordSample / IsConverged on the crafted streams of
+                         tests/pixel_stat_cases.py, for several (rel_threshold, min_spp)
   render_<case>.npz      seeded single-thread renders (mt RNG): linear fb, spp, P3 PPM bytes
   textures/earthmap.ppm  the reference's decoded earthmap texels (Image after stb + FloatToByte)
 
@@ -247,6 +249,26 @@ def main():
     run("pixelstate", os.path.join(tmp, "ps.f64"), os.path.join(tmp, "ps.out"))
     np.savez_compressed(os.path.join(GOLD, "pixelstate.npz"), seq=seq,
                         out=np.fromfile(os.path.join(tmp, "ps.out"), dtype=np.float64).reshape(-1, 10))
+
+    # ... and on the crafted edge streams of tests/pixel_stat_cases.py, for several (rel, min_spp):
+    # the statistics do not depend on the pair (checked), so they are kept once, and the
+    # IsConverged column once per pair
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import pixel_stat_cases as psc
+    eseq = psc.pack_streams(psc.fixture_streams())
+    eseq.tofile(os.path.join(tmp, "pse.f64"))
+    eout, econv = None, []
+    for rel, mn in psc.PAIRS:
+        run("pixelstate", os.path.join(tmp, "pse.f64"), os.path.join(tmp, "pse.out"),
+            float(rel).hex() if np.isfinite(rel) else repr(float(rel)), mn)
+        o = np.fromfile(os.path.join(tmp, "pse.out"), dtype=np.float64).reshape(-1, 10)
+        if eout is None:
+            eout = o
+        assert np.array_equal(o[:, :9].view(np.uint64), eout[:, :9].view(np.uint64))
+        econv.append(o[:, 9].astype(np.uint8))
+    np.savez_compressed(os.path.join(GOLD, "pixelstate_edges.npz"), seq=eseq, out=eout[:, :9],
+                        rel=np.array([p[0] for p in psc.PAIRS]), min_spp=np.array([p[1] for p in psc.PAIRS]),
+                        conv=np.array(econv))
 
     # seeded single-thread renders
     manifest = {}

@@ -714,7 +714,7 @@ void usage() {
                "ref_harness scatter <cases.f64> <out.f64>\n"
                "ref_harness texture <cases.f64> <out.f64>\n"
                "ref_harness texels <out.ppm>\n"
-               "ref_harness pixelstate <samples.f64> <out.f64>\n"
+               "ref_harness pixelstate <samples.f64> <out.f64> [<rel> <min_spp>]\n"
                "ref_harness render <scene.rtxs> <model_dir> <cam 14 numbers> <maxdepth> <spp> <adaptive> "
                "<seed> <out_prefix>\n"
                "ref_harness megakernel <scene.rtxs> <model_dir> <cam 14 numbers> <maxdepth> <spp> <seed> "
@@ -913,8 +913,12 @@ int main(int argc, char** argv) {
     o << "P6\n" << img.Width() << ' ' << img.Height() << "\n255\n";
     for (int y = 0; y < img.Height(); y++)
       for (int x = 0; x < img.Width(); x++) o.write((const char*)img.PixelData(x, y), 3);
-  } else if (cmd == "pixelstate" && argc == 4) {
+  } else if (cmd == "pixelstate" && (argc == 4 || argc == 6)) {
     // input: sequences of (n, then n samples of 3 doubles) ; output per record: mean3 m2 3 sum3 conv
+    // optional <rel> <min_spp>: IsConverged's arguments (rel as the double strtod reads: hex
+    // floats, inf), else the wavefront renderer's kRelThresh 0.05f and kMinSamples 16
+    const double rel = argc == 6 ? std::strtod(argv[4], nullptr) : (double)0.05f;
+    const int min_spp = argc == 6 ? std::atoi(argv[5]) : 16;
     auto c = read_bin<double>(argv[2]);
     std::vector<double> out;
     size_t k = 0;
@@ -924,7 +928,7 @@ int main(int argc, char** argv) {
       for (int i = 0; i < n; i++) {
         integrator::RecordSample(ps, Color(c[k], c[k + 1], c[k + 2]));
         k += 3;
-        bool conv = integrator::IsConverged(ps, 0.05f, 16);
+        bool conv = integrator::IsConverged(ps, rel, min_spp);
         out.insert(out.end(), {ps.mean.x(), ps.mean.y(), ps.mean.z(), ps.m2.x(), ps.m2.y(), ps.m2.z(),
                                ps.sum.x(), ps.sum.y(), ps.sum.z(), (double)conv});
       }

@@ -992,6 +992,32 @@ inline double luminance(V3 c) {  // color.h:35-37 (float weights)
   return 0.2126f * c.x + 0.7152f * c.y + 0.0722f * c.z;
 }
 
+// AdaptiveSampler::SamplePixel's loop (sampler.h:44-82) over the samples next(k) hands it, k =
+// 0, 1, ...: `pixel` is the running sum of the samples, sum / sum_sq those of the running sums,
+// and the loop runs while samples <= max_samples.  Returns the samples taken; the caller divides
+// pixel by them.  (render_megakernel and orc_pixel_replay share it.)
+template <class Next>
+inline int mk_adaptive_pixel(int min_samples, int max_samples, double threshold, Next next, V3& pixel, V3& sum,
+                             V3& sum_sq) {
+  int samples = 0;
+  pixel = sum = sum_sq = V3{0, 0, 0};
+  while (samples <= max_samples) {
+    const V3 x = next(samples);
+    samples++;
+    pixel = pixel + x;
+    sum = sum + pixel;
+    sum_sq = sum_sq + pixel * pixel;
+    if (samples >= min_samples) {
+      V3 mean = sum / samples;
+      double mean_luminance = luminance(mean);
+      V3 variance = (sum_sq / samples) - (mean * mean);
+      double error = std::sqrt(luminance(variance) / samples);
+      if ((error / (mean_luminance + 1e-3f)) < threshold) break;
+    }
+  }
+  return samples;
+}
+
 void render_megakernel(const Scene& S, const Camera& cam, const Params& P, double* fb, int* spp_out, Stats& st) {
   const int W = cam.width;
   const bool mt_mode = P.rng_mode == 0;
@@ -1018,23 +1044,13 @@ void render_megakernel(const Scene& S, const Camera& cam, const Params& P, doubl
         pixel = pixel / P.spp;
         samples = P.spp;
       } else {  // AdaptiveSampler::SamplePixel (sampler.h:44-82): `pixel` is the running sum
-        V3 sum{0, 0, 0}, sum_sq{0, 0, 0};
-        while (samples <= P.spp) {
-          g.sample = samples, g.open(0);
-          samples++;
+        V3 sum, sum_sq;
+        samples = mk_adaptive_pixel(P.mk_min_samples, P.spp, P.mk_threshold, [&](int k) {
+          g.sample = k, g.open(0);
           V3 o, d;
           cam.get_ray(x, y, g, o, d);
-          pixel = pixel + get_pixel(S, o, d, P.max_depth, P.max_depth, g, rays);
-          sum = sum + pixel;
-          sum_sq = sum_sq + pixel * pixel;
-          if (samples >= P.mk_min_samples) {
-            V3 mean = sum / samples;
-            double mean_luminance = luminance(mean);
-            V3 variance = (sum_sq / samples) - (mean * mean);
-            double error = std::sqrt(luminance(variance) / samples);
-            if ((error / (mean_luminance + 1e-3f)) < P.mk_threshold) break;
-          }
-        }
+          return get_pixel(S, o, d, P.max_depth, P.max_depth, g, rays);
+        }, pixel, sum, sum_sq);
         pixel = pixel / samples;
       }
       size_t oi = (size_t)ty * tw + tx;
@@ -1389,6 +1405,63 @@ int orc_pixelstate(const double* in, long long nin, double* out) {
       std::memcpy(out + o, r, sizeof r);
       o += 10;
     }
+  }
+  return 0;
+}
+// A caller's table of radiance samples through the pixel statistics: pixel p takes
+// table[p][0 .. budget) (3 doubles each) in order.
+//   mode 0  RecordSample + IsConverged(rel, min_spp) after every sample, stopping at convergence
+//           or at the budget (the wavefront renderer's pixel); rgb = sum / (float)samples
+//   mode 1  fixed spp: every sample recorded, no convergence test; rgb = sum / (float)budget, and
+//           rgb_spp (may be NULL) the DefaultSampler's pixel / spp
+//   mode 2  AdaptiveSampler(min_spp, budget - 1, rel): sum = pixel (the running sum), mean / m2 =
+//           its sum / sum_sq, conv = 1; rgb = pixel / samples
+// sum, mean, m2, rgb: 3 doubles per pixel; samples: int; conv: one byte.  records (modes 0 and 1,
+// may be NULL): orc_pixelstate's record (mean m2 sum conv, 10 doubles) after EVERY sample of the
+// table, the ones past the pixel's convergence included (the statistics go on as if it had not
+// stopped; the pixel's own outputs are those at the stop).
+int orc_pixel_replay(int mode, const double* table, long long npix, int budget, int min_spp, double rel,
+                     double* sum, double* mean, double* m2, int* samples, unsigned char* conv, double* rgb,
+                     double* rgb_spp, double* records) {
+  if (mode < 0 || mode > 2 || budget < 0 || npix < 0) {
+    g_err = "orc_pixel_replay: bad arguments";
+    return -1;
+  }
+  for (long long p = 0; p < npix; p++) {
+    const double* t = table + 3 * p * (long long)budget;
+    PixelState fin;
+    if (mode == 2) {
+      V3 pixel, s, sq;
+      fin.samples = mk_adaptive_pixel(min_spp, budget - 1, rel, [&](int k) { return v3(t[3 * k], t[3 * k + 1], t[3 * k + 2]); },
+                                      pixel, s, sq);
+      for (int c = 0; c < 3; c++) fin.sum[c] = pixel[c], fin.mean[c] = s[c], fin.m2[c] = sq[c];
+      fin.converged = true;
+      const V3 out = pixel / fin.samples;
+      for (int c = 0; c < 3; c++) rgb[3 * p + c] = out[c];
+    } else {
+      PixelState ps;
+      bool stopped = false;
+      for (int k = 0; k < budget && !(stopped && !records); k++) {
+        record_sample(ps, v3(t[3 * k], t[3 * k + 1], t[3 * k + 2]));
+        const bool c = mode == 0 && is_converged(ps, rel, min_spp);
+        if (records) {
+          double r[10] = {ps.mean[0], ps.mean[1], ps.mean[2], ps.m2[0], ps.m2[1],
+                          ps.m2[2],   ps.sum[0],  ps.sum[1],  ps.sum[2], (double)c};
+          std::memcpy(records + 10 * (p * (long long)budget + k), r, sizeof r);
+        }
+        if (c && !stopped) fin = ps, fin.converged = true, stopped = true;
+      }
+      if (!stopped) fin = ps;
+      const double inv = fin.samples > 0 ? 1.0 / (double)(float)fin.samples : 0.0;
+      for (int c = 0; c < 3; c++) rgb[3 * p + c] = fin.samples > 0 ? inv * fin.sum[c] : 0.0;
+      if (rgb_spp) {
+        const V3 out = v3(fin.sum[0], fin.sum[1], fin.sum[2]) / budget;
+        for (int c = 0; c < 3; c++) rgb_spp[3 * p + c] = out[c];
+      }
+    }
+    for (int c = 0; c < 3; c++) sum[3 * p + c] = fin.sum[c], mean[3 * p + c] = fin.mean[c], m2[3 * p + c] = fin.m2[c];
+    samples[p] = fin.samples;
+    conv[p] = fin.converged ? 1 : 0;
   }
   return 0;
 }

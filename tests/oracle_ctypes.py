@@ -52,6 +52,8 @@ def lib():
         L.orc_material.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int]
         L.orc_texture.argtypes = [C.c_void_p, C.c_longlong, C.c_char_p, C.c_void_p]
         L.orc_pixelstate.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p]
+        L.orc_pixel_replay.argtypes = [C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_double] + \
+            [C.c_void_p] * 8
         L.orc_camera_init.argtypes = [C.POINTER(OrcCamera), C.c_void_p]
         L.orc_render.argtypes = [C.c_void_p, C.POINTER(OrcCamera), C.POINTER(OrcParams), C.c_void_p, C.c_void_p,
                                  C.c_void_p]
@@ -251,6 +253,33 @@ def pixelstate(seq):
     out = np.zeros((n, 10))
     lib().orc_pixelstate(_ptr(seq), len(seq), _ptr(out))
     return out
+
+
+REPLAY_MODES = {"adaptive": 0, "fixed": 1, "mk_adaptive": 2}
+
+
+def pixel_replay(mode, table, min_spp, rel, records=False):
+    """A table of radiance samples [npix, budget, 3] through the pixel statistics
+    (orc_pixel_replay): "adaptive" RecordSample + IsConverged(rel, min_spp) to convergence or the
+    budget, "fixed" every sample, "mk_adaptive" AdaptiveSampler(min_spp, budget - 1, rel).
+    Returns sum, mean, m2, rgb [npix, 3], samples, conv [npix]; "fixed": also rgb_spp (the
+    DefaultSampler's pixel / spp); records=True: the record after every sample [npix, budget, 10]."""
+    table = np.ascontiguousarray(table, dtype=np.float64)
+    npix, budget = table.shape[:2]
+    assert table.shape == (npix, budget, 3)
+    r = {k: np.zeros((npix, 3)) for k in ("sum", "mean", "m2", "rgb")}
+    r["samples"], r["conv"] = np.zeros(npix, np.int32), np.zeros(npix, np.uint8)
+    if mode == "fixed":
+        r["rgb_spp"] = np.zeros((npix, 3))
+    if records:
+        r["records"] = np.zeros((npix, budget, 10))
+    rc = lib().orc_pixel_replay(REPLAY_MODES[mode], _ptr(table), npix, budget, int(min_spp), float(rel), _ptr(r["sum"]),
+                                _ptr(r["mean"]), _ptr(r["m2"]), _ptr(r["samples"]), _ptr(r["conv"]), _ptr(r["rgb"]),
+                                _ptr(r["rgb_spp"]) if mode == "fixed" else None,
+                                _ptr(r["records"]) if records else None)
+    if rc != 0:
+        raise RuntimeError(lib().orc_last_error().decode())
+    return r
 
 
 def philox(seed, pixel, sample, n, stream=0):

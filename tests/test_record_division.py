@@ -4,7 +4,12 @@ Markstein correction must equal the IEEE quotient bit for bit.  A small C progra
 -ffp-contract=off, the C library's fma) checks random, integer-multiple and near-tie dividends
 for every count up to 4096, and for sampled larger counts up to 2^31 (every power of two and its
 neighbours, random counts between): the API accepts any spp budget, and the samples counter is
-32-bit."""
+32-bit.
+
+This checks a host copy of the function.  The device's own text, its fallbacks included (|delta|
+below 2^-900, zero and non-finite deltas take the division), runs in
+tests/test_gpu_pixel_stats.py: the "magnitudes" and "non_finite" rows of
+tests/pixel_stat_cases.py through the adaptive replay, against the oracle's division."""
 import os
 import subprocess
 
