@@ -103,6 +103,10 @@ constexpr uint32_t kRngStreamIrr = 0xA1000000u;
 // The direct-lighting queries' emitter samples (rtx_direct.h): another value above every
 // segment's stream, so it collides with none of the above.
 constexpr uint32_t kRngStreamDirect = 0xA2000000u;
+// The emitter samples of next-event estimation (rtx_nee.h): the vertex of segment d draws from
+// kRngStreamNee + d, d < max_depth <= 0x00FFFFFF (the entry points' cap), so the streams fill
+// [0xA3000000, 0xA3FFFFFF]: above every segment's stream and apart from the three values above.
+constexpr uint32_t kRngStreamNee = 0xA3000000u;
 __device__ __forceinline__ void philox_block(uint32_t blk, uint32_t sample, uint32_t pixel, uint32_t stream,
                                              uint32_t k0, uint32_t k1, double& u0, double& u1) {
   uint32_t c0 = blk, c1 = sample, c2 = pixel, c3 = stream;

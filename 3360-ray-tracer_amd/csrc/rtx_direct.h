@@ -99,8 +99,11 @@ __global__ __launch_bounds__(kBlock) void k_emitter_scan(EmitterTable E) {
 // false, with o, d and C zero: nothing to trace.  No emitters, A not > 0 or not finite; a
 // degenerate normal (irradiance_ray's test); |y - x|^2 not > 0 or not finite; or no component of
 // C > 0 (a light that faces away or is seen edge-on, a black light, a NaN).
-__device__ __forceinline__ bool direct_sample(const DScene& S, const EmitterTable& E, uint64_t seed, uint32_t pix,
-                                              uint32_t smp, const rtx_ray& s, V3& o, V3& d, V3& C) {
+// direct_sample_from: the same from `stream` of the key (next-event estimation draws a path
+// vertex's sample from a stream of its own, rtx_nee.h).
+__device__ __forceinline__ bool direct_sample_from(const DScene& S, const EmitterTable& E, uint64_t seed, uint32_t pix,
+                                                   uint32_t smp, uint32_t stream, const rtx_ray& s, V3& o, V3& d,
+                                                   V3& C) {
   o = v3(0, 0, 0), d = v3(0, 0, 0), C = v3(0, 0, 0);
   if (E.n <= 0) return false;
   const double A = E.cum[E.n - 1];
@@ -109,7 +112,7 @@ __device__ __forceinline__ bool direct_sample(const DScene& S, const EmitterTabl
   const double l2 = len2(n);
   if (!(l2 > 0.0) || !(l2 < kInf)) return false;
   const V3 x = v3(s.origin[0], s.origin[1], s.origin[2]);
-  Rng g = make_rng(seed, pix, smp, kRngStreamDirect);
+  Rng g = make_rng(seed, pix, smp, stream);
   const double u0 = g.next(), u1 = g.next(), u2 = g.next();
   // the first entry above u0 * A; the last one when the product rounds up to A
   const double target = u0 * A;
@@ -161,6 +164,10 @@ __device__ __forceinline__ bool direct_sample(const DScene& S, const EmitterTabl
   if (!(c.x > 0.0 || c.y > 0.0 || c.z > 0.0)) return false;
   o = x, d = seg, C = c;
   return true;
+}
+__device__ __forceinline__ bool direct_sample(const DScene& S, const EmitterTable& E, uint64_t seed, uint32_t pix,
+                                              uint32_t smp, const rtx_ray& s, V3& o, V3& d, V3& C) {
+  return direct_sample_from(S, E, seed, pix, smp, kRngStreamDirect, s, o, d, C);
 }
 
 // One lane per slot of the chunk (RadianceChunk: `rays` are the surfels; max_depth is not read):

@@ -1,7 +1,8 @@
 // rtx_queries.hip — the ray-query entry points of the C ABI (include/rtx.h) and their kernels:
 // closest hit (rtx_intersect*), any hit and the AO pass (rtx_occluded*, rtx_ao*), first-hit AOVs
 // (rtx_aov*), radiance, irradiance and direct lighting on caller-supplied rays and surfels
-// (rtx_radiance*, rtx_irradiance*, rtx_direct*, rtx_scene_emitters), with their test hooks.
+// (rtx_radiance*, rtx_irradiance*, rtx_direct*, rtx_scene_emitters), the light-sampling estimator
+// on rays and on the camera's own frame (rtx_radiance_nee*, rtx_render_nee*), with their test hooks.
 // Scenes, films and the frame renderer are rtx_capi.hip's; the two share rtx_host.h.  Every query
 // picks its walk with with_walk (fast only with a fast tree, the scene's stack size).
 #include <atomic>
@@ -12,6 +13,7 @@
 #include "rtx_radiance.h"
 #include "rtx_irradiance.h"
 #include "rtx_direct.h"
+#include "rtx_nee.h"
 #include "rtx_shade_steps.h"
 #define RTX_DENOISE_AOV_KERNELS  // this translation unit holds k_aov (it needs the trace kernels)
 #include "rtx_denoise.h"
@@ -72,8 +74,9 @@ int ao_check(const rtx_scene* sc, const rtx_camera* cam, const rtx_render_params
 // the slot cap of the calls that follow (rtx_internal_radiance_chunk; 0: kRadianceSlots)
 std::atomic<int64_t> g_radiance_chunk{0};
 // what a chunk's slots hold (radiance_on): a path from a caller's ray, a path from a surfel's
-// hemisphere sample, or a surfel's emitter sample
-enum SlotKind { kSlotRadiance = 0, kSlotIrradiance = 1, kSlotDirect = 2 };
+// hemisphere sample, a surfel's emitter sample, or a path with next-event estimation (from a
+// caller's ray, or from the camera when radiance_on is given one)
+enum SlotKind { kSlotRadiance = 0, kSlotIrradiance = 1, kSlotDirect = 2, kSlotNee = 3 };
 // the checks rtx_radiance*, rtx_irradiance*, rtx_direct* and their test hooks share, in the documented order
 int radiance_check(const rtx_scene* sc, const rtx_radiance_params* prm, const void* rays, const void* out) {
   if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
@@ -87,15 +90,22 @@ int radiance_check(const rtx_scene* sc, const rtx_radiance_params* prm, const vo
     return fail(RTX_ERR_INVALID, "radiance: bad precision");
   return RTX_OK;
 }
+// next-event estimation: the vertex of segment d draws from stream kRngStreamNee + d, d < max_depth
+int nee_depth_check(int32_t max_depth) {
+  if (max_depth > 0x00FFFFFF) return fail(RTX_ERR_INVALID, "nee: max_depth above 16777215 (0x00FFFFFF)");
+  return RTX_OK;
+}
 // n > 0 rays on device buffers, in chunks of at most `cap` slots (ray x sample): whole rays per
 // chunk, or, when one ray's samples exceed the cap, one ray at a time in runs of `cap` samples
 // whose partial sum k_radiance_sum carries.  id_base: the pixel key of d_rays[0] when d_ids is
 // null (the host entry point's batches).  what: for kSlotIrradiance and kSlotDirect d_rays are
 // surfels and the slots are k_irradiance's (rtx_irradiance*) or k_direct's (rtx_direct*: a
 // slot's "segments" are its visibility, 0 or 1); the chunking, the scratch and the sum are the same.
+// kSlotNee: k_radiance_nee's slots, or with `cam` k_render_nee's: the "rays" are then the n pixels
+// of the camera's subset in subset order (d_rays and d_ids are not read).
 int radiance_on(rtx_scene* sc, const rtx_ray* d_rays, const uint32_t* d_ids, uint64_t id_base, int64_t n,
                 const rtx_radiance_params* prm, double* d_out, uint32_t* d_segs, hipStream_t s,
-                SlotKind what = kSlotRadiance) {
+                SlotKind what = kSlotRadiance, const NeeCamera* cam = nullptr) {
   const int64_t tuned = g_radiance_chunk.load();
   const int64_t cap = std::min<int64_t>(tuned > 0 ? tuned : kRadianceSlots, kRadianceSlotsMax);
   const int64_t spp = prm->spp;
@@ -123,6 +133,10 @@ int radiance_on(rtx_scene* sc, const rtx_ray* d_rays, const uint32_t* d_ids, uin
         switch (what) {
           case kSlotDirect: rc = launch_1d(k_direct<w.stack, w.fast>, A.slots, lds, s, sc->S, emitter_table(sc), A); break;
           case kSlotIrradiance: rc = launch_1d(k_irradiance<w.stack, w.fast>, A.slots, lds, s, sc->S, A); break;
+          case kSlotNee:
+            if (cam) rc = launch_1d(k_render_nee<w.stack, w.fast>, A.slots, lds, s, sc->S, emitter_table(sc), A, *cam);
+            else rc = launch_1d(k_radiance_nee<w.stack, w.fast>, A.slots, lds, s, sc->S, emitter_table(sc), A);
+            break;
           default: rc = launch_1d(k_radiance<w.stack, w.fast>, A.slots, lds, s, sc->S, A);
         }
         if (rc) return rc;
@@ -143,6 +157,7 @@ int radiance_host(rtx_scene* sc, const rtx_ray* rays, const uint32_t* ids, size_
                   double* out_rgb, uint32_t* out_segments, SlotKind what) {
   int rc;
   if ((rc = radiance_check(sc, prm, rays, out_rgb))) return rc;
+  if (what == kSlotNee && (rc = nee_depth_check(prm->max_depth))) return rc;
   if (n == 0) return RTX_OK;
   HIPC(hipSetDevice(sc->device));
   const size_t m = std::min(n, kRadianceHostRays);
@@ -181,6 +196,7 @@ int radiance_device(rtx_scene* sc, const rtx_ray* d_rays, const uint32_t* d_ids,
                     SlotKind what) {
   int rc;
   if ((rc = radiance_check(sc, prm, d_rays, d_out_rgb))) return rc;
+  if (what == kSlotNee && (rc = nee_depth_check(prm->max_depth))) return rc;
   if (n == 0) return RTX_OK;
   HIPC(hipSetDevice(sc->device));
   return radiance_on(sc, d_rays, d_ids, 0, (int64_t)n, prm, d_out_rgb, d_out_segments,
@@ -191,9 +207,10 @@ int radiance_device(rtx_scene* sc, const rtx_ray* d_rays, const uint32_t* d_ids,
 // scratch (`per_slot` doubles per slot) and the copy back to the host.
 template <class Launch>
 int surfel_samples(rtx_scene* sc, const rtx_ray* surfels, const uint32_t* ids, size_t n, const rtx_radiance_params* prm,
-                   double* out, size_t per_slot, const char* too_many, Launch launch) {
+                   double* out, size_t per_slot, const char* too_many, Launch launch, const char* bad_extra = nullptr) {
   int rc;
   if ((rc = radiance_check(sc, prm, surfels, out))) return rc;
+  if (bad_extra) return fail(RTX_ERR_INVALID, bad_extra);  // (a hook's own argument, after the shared checks)
   if (n == 0) return RTX_OK;
   if (n > (size_t)kRadianceSlotsMax || (int64_t)n * prm->spp > kRadianceSlotsMax) return fail(RTX_ERR_INVALID, too_many);
   HIPC(hipSetDevice(sc->device));
@@ -208,6 +225,28 @@ int surfel_samples(rtx_scene* sc, const rtx_ray* surfels, const uint32_t* ids, s
     return rc;
   HIPC(hipMemcpyAsync(out, sc->rad_L.p, bytes, hipMemcpyDeviceToHost, sc->stream));
   HIPC(hipStreamSynchronize(sc->stream));
+  return RTX_OK;
+}
+// ---- frames with next-event estimation (rtx_nee.h) ----
+// the checks rtx_render_nee and rtx_render_nee_device share, in the documented order; *npix:
+// pixels of the subset; rp: the render params read as the radiance family reads its own
+int render_nee_check(const rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, NeeCamera& nc,
+                     int64_t* npix, rtx_radiance_params& rp) {
+  if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
+  if (!cam || !prm) return fail(RTX_ERR_INVALID, "NULL argument");
+  if (prm->spp < 1) return fail(RTX_ERR_INVALID, "render nee: spp must be at least 1");
+  if (prm->max_depth < 0) return fail(RTX_ERR_INVALID, "negative max_depth");
+  int rc;
+  if ((rc = nee_depth_check(prm->max_depth))) return rc;
+  if (prm->adaptive != 0) return fail(RTX_ERR_INVALID, "render nee: adaptive sampling is not supported (fixed spp only)");
+  if (prm->precision != RTX_PREC_PARITY && prm->precision != RTX_PREC_FAST)
+    return fail(RTX_ERR_INVALID, "render nee: bad precision");
+  std::string err;
+  *npix = subset_pixels(cam, prm, nc.map, err);
+  if (*npix < 0) return fail(RTX_ERR_INVALID, err);
+  nc.cam = *cam;
+  rp.spp = prm->spp, rp.max_depth = prm->max_depth, rp.first_sample = 0, rp.precision = prm->precision;
+  rp.seed = prm->seed;
   return RTX_OK;
 }
 }  // namespace
@@ -447,6 +486,121 @@ int rtx_internal_emitters(rtx_scene* sc, int64_t* prims_out, double* cum_out, in
     HIPC(hipStreamSynchronize(sc->stream));
     HIPC(hipMemcpy(cum_out, sc->emit_cum.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
   }
+  return RTX_OK;
+}
+
+// ---- next-event estimation (rtx_nee.h): rtx_radiance's checks, chunks and staging ----
+int rtx_radiance_nee_device(rtx_scene* sc, const rtx_ray* d_rays, const uint32_t* d_ids, size_t n,
+                            const rtx_radiance_params* prm, double* d_out_rgb, uint32_t* d_out_segments,
+                            void* stream) {
+  return radiance_device(sc, d_rays, d_ids, n, prm, d_out_rgb, d_out_segments, stream, kSlotNee);
+}
+int rtx_radiance_nee(rtx_scene* sc, const rtx_ray* rays, const uint32_t* ids, size_t n, const rtx_radiance_params* prm,
+                     double* out_rgb, uint32_t* out_segments) {
+  return radiance_host(sc, rays, ids, n, prm, out_rgb, out_segments, kSlotNee);
+}
+
+int rtx_render_nee_device(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, double* d_out_rgb,
+                          uint32_t* d_out_segments, void* stream) {
+  NeeCamera nc;
+  int64_t npix;
+  rtx_radiance_params rp{};
+  int rc;
+  if ((rc = render_nee_check(sc, cam, prm, nc, &npix, rp))) return rc;
+  if (npix == 0) return RTX_OK;
+  if (!d_out_rgb) return fail(RTX_ERR_INVALID, "NULL buffer");
+  HIPC(hipSetDevice(sc->device));
+  return radiance_on(sc, nullptr, nullptr, 0, npix, &rp, d_out_rgb, d_out_segments,
+                     stream ? (hipStream_t)stream : sc->stream, kSlotNee, &nc);
+}
+
+int rtx_render_nee(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, double* out_rgb,
+                   uint32_t* out_segments) {
+  NeeCamera nc;
+  int64_t npix;
+  rtx_radiance_params rp{};
+  int rc;
+  if ((rc = render_nee_check(sc, cam, prm, nc, &npix, rp))) return rc;
+  if (npix == 0) return RTX_OK;
+  if (!out_rgb) return fail(RTX_ERR_INVALID, "NULL buffer");
+  HIPC(hipSetDevice(sc->device));
+  if ((rc = sc->rad_out.reserve((size_t)npix * 3 * sizeof(double)))) return rc;
+  if ((rc = sc->rad_oseg.reserve((size_t)npix * sizeof(uint32_t)))) return rc;
+  if ((rc = radiance_on(sc, nullptr, nullptr, 0, npix, &rp, sc->rad_out.as<double>(), sc->rad_oseg.as<uint32_t>(),
+                        sc->stream, kSlotNee, &nc)))
+    return rc;
+  HIPC(hipMemcpyAsync(out_rgb, sc->rad_out.p, (size_t)npix * 3 * sizeof(double), hipMemcpyDeviceToHost, sc->stream));
+  if (out_segments)
+    HIPC(hipMemcpyAsync(out_segments, sc->rad_oseg.p, (size_t)npix * sizeof(uint32_t), hipMemcpyDeviceToHost, sc->stream));
+  HIPC(hipStreamSynchronize(sc->stream));
+  return RTX_OK;
+}
+
+// Test hook (not in rtx.h): rtx_internal_direct_samples on stream kRngStreamNee + depth, the
+// samples a path of rtx_radiance_nee draws at a vertex of that depth (k_nee_samples, rtx_nee.h);
+// depth outside 0 .. 0x00FFFFFE is RTX_ERR_INVALID after the shared checks.  Host buffers.
+int rtx_internal_nee_samples(rtx_scene* sc, const rtx_ray* surfels, const uint32_t* ids, size_t n,
+                             const rtx_radiance_params* prm, int32_t depth, double* out) {
+  return surfel_samples(
+      sc, surfels, ids, n, prm, out, 9, "nee samples: too many samples for one call",
+      [&](uint32_t nslots, const rtx_ray* d_surfels, const uint32_t* d_ids, double* d_out) {
+        return launch_1d(k_nee_samples, nslots, 0, sc->stream, sc->S, emitter_table(sc), d_surfels, d_ids, nslots,
+                         (uint32_t)prm->spp, prm->seed, prm->first_sample, (uint32_t)depth, d_out);
+      },
+      depth < 0 || depth >= 0x00FFFFFF ? "nee samples: depth outside 0..16777214" : nullptr);
+}
+
+// Test hook (not in rtx.h): the paths of rtx_radiance_nee for the same rays, keys and params, one
+// slot per (ray, sample), ray major, from the device function its kernel runs (nee_path through
+// k_nee_trace, rtx_nee.h).  Per slot and segment d < cap: verts 9 doubles (vertex point, shading
+// normal, w = thr * rho; zero on a miss, w zero where no term is eligible) and one flag word
+// (1 term eligible, 2 sample traced, 4 visible, 8 the path ended here on an emitter whose emission
+// is suppressed); segments a path does not reach stay zero.  Per slot: ends 3 doubles (L_end) and
+// counts 2 uint32 (closest-hit segments, shadow segments traced).  cap in 1..4096.  Host buffers.
+int rtx_internal_nee_trace(rtx_scene* sc, const rtx_ray* rays, const uint32_t* ids, size_t n,
+                           const rtx_radiance_params* prm, int32_t cap, double* verts, uint32_t* flags, double* ends,
+                           uint32_t* counts) {
+  int rc;
+  if ((rc = radiance_check(sc, prm, rays, verts))) return rc;
+  if ((rc = nee_depth_check(prm->max_depth))) return rc;
+  if (!flags || !ends || !counts) return fail(RTX_ERR_INVALID, "NULL buffer");
+  if (cap < 1 || cap > 4096) return fail(RTX_ERR_INVALID, "nee trace: cap outside 1..4096");
+  if (n == 0) return RTX_OK;
+  if (n > ((size_t)1 << 20) || (int64_t)n * prm->spp * cap > ((int64_t)1 << 22))
+    return fail(RTX_ERR_INVALID, "nee trace: too many records for one call");
+  HIPC(hipSetDevice(sc->device));
+  const size_t nslots = n * (size_t)prm->spp, nrec = nslots * (size_t)cap;
+  // doubles: verts | ends (rad_L); words: flags | counts (rad_segs)
+  const size_t b_verts = nrec * 9 * sizeof(double), b_ends = nslots * 3 * sizeof(double);
+  const size_t b_flags = nrec * sizeof(uint32_t), b_counts = nslots * 2 * sizeof(uint32_t);
+  if ((rc = sc->rays.reserve(n * sizeof(rtx_ray)))) return rc;
+  if ((rc = sc->rad_L.reserve(b_verts + b_ends))) return rc;
+  if ((rc = sc->rad_segs.reserve(b_flags + b_counts))) return rc;
+  if (ids && (rc = sc->rad_ids.reserve(n * sizeof(uint32_t)))) return rc;
+  hipStream_t s = sc->stream;
+  HIPC(hipMemcpyAsync(sc->rays.p, rays, n * sizeof(rtx_ray), hipMemcpyHostToDevice, s));
+  if (ids) HIPC(hipMemcpyAsync(sc->rad_ids.p, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  HIPC(hipMemsetAsync(sc->rad_L.p, 0, b_verts + b_ends, s));
+  HIPC(hipMemsetAsync(sc->rad_segs.p, 0, b_flags + b_counts, s));
+  double* const d_verts = sc->rad_L.as<double>();
+  double* const d_ends = d_verts + nrec * 9;
+  uint32_t* const d_flags = sc->rad_segs.as<uint32_t>();
+  uint32_t* const d_counts = d_flags + nrec;
+  RadianceChunk A;
+  A.rays = sc->rays.as<rtx_ray>(), A.ids = ids ? sc->rad_ids.as<uint32_t>() : nullptr, A.ray0 = 0, A.id_base = 0;
+  A.slots = (uint32_t)nslots, A.K = (uint32_t)prm->spp;
+  A.s0 = prm->first_sample, A.max_depth = prm->max_depth, A.seed = prm->seed;
+  A.L = nullptr, A.segs = nullptr;  // (not written by k_nee_trace)
+  if ((rc = with_walk(sc, prm->precision, [&](auto w) {
+         return launch_1d(k_nee_trace<w.stack, w.fast>, (int64_t)nslots, stack_lds_bytes(w.stack), s, sc->S,
+                          emitter_table(sc), A, cap, d_verts, d_flags, d_ends, d_counts);
+       })))
+    return rc;
+  HIPC(hipMemcpyAsync(verts, d_verts, b_verts, hipMemcpyDeviceToHost, s));
+  HIPC(hipMemcpyAsync(ends, d_ends, b_ends, hipMemcpyDeviceToHost, s));
+  HIPC(hipMemcpyAsync(flags, d_flags, b_flags, hipMemcpyDeviceToHost, s));
+  HIPC(hipMemcpyAsync(counts, d_counts, b_counts, hipMemcpyDeviceToHost, s));
+  HIPC(hipStreamSynchronize(s));
   return RTX_OK;
 }
 

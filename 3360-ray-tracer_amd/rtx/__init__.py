@@ -145,7 +145,8 @@ EXPORTS = ["rtx_abi_version", "rtx_last_error", "rtx_device_count", "rtx_scene_c
            "rtx_denoise_device", "rtx_film_denoise", "rtx_film_denoise_p3", "rtx_scene_update_prims",
            "rtx_scene_update_geometry_device", "rtx_scene_epoch", "rtx_bvh_refit_host", "rtx_film_reset",
            "rtx_occluded", "rtx_occluded_device", "rtx_ao", "rtx_ao_device", "rtx_radiance", "rtx_radiance_device",
-           "rtx_irradiance", "rtx_irradiance_device", "rtx_direct", "rtx_direct_device", "rtx_scene_emitters"]
+           "rtx_irradiance", "rtx_irradiance_device", "rtx_direct", "rtx_direct_device", "rtx_scene_emitters",
+           "rtx_radiance_nee", "rtx_radiance_nee_device", "rtx_render_nee", "rtx_render_nee_device"]
 
 _lib = None
 
@@ -224,6 +225,10 @@ def lib():
             "rtx_direct": ([vp, vp, vp, sz, C.POINTER(RadianceParams), vp, vp], C.c_int),
             "rtx_direct_device": ([vp, vp, vp, sz, C.POINTER(RadianceParams), vp, vp, vp], C.c_int),
             "rtx_scene_emitters": ([vp, C.POINTER(C.c_int64), C.POINTER(C.c_double)], C.c_int),
+            "rtx_radiance_nee": ([vp, vp, vp, sz, C.POINTER(RadianceParams), vp, vp], C.c_int),
+            "rtx_radiance_nee_device": ([vp, vp, vp, sz, C.POINTER(RadianceParams), vp, vp, vp], C.c_int),
+            "rtx_render_nee": ([vp, C.POINTER(Camera), C.POINTER(RenderParams), vp, vp], C.c_int),
+            "rtx_render_nee_device": ([vp, C.POINTER(Camera), C.POINTER(RenderParams), vp, vp, vp], C.c_int),
         }
         for name, (args, res) in sig.items():
             f = getattr(L, name)
@@ -518,6 +523,74 @@ class DeviceScene:
         n, a = C.c_int64(0), C.c_double(0.0)
         _check(lib().rtx_scene_emitters(self.h, C.byref(n), C.byref(a)), "rtx_scene_emitters")
         return n.value, a.value
+
+    def radiance_nee(self, rays, spp, max_depth, seed=1234, ids=None, first_sample=0, precision="parity",
+                     segments=False):
+        """Radiance query with next-event estimation (rtx_radiance_nee): radiance()'s arguments,
+        paths and keys; at every vertex where a Lambertian scattered (and depth + 1 < max_depth) one
+        emitter sample of direct() is added, weighted by the path's throughput and the surface's
+        reflectance, and an emitter hit right after such a vertex counts 0.  The same expectation
+        as radiance() with far less variance where lights are small; without emitters, or with
+        max_depth <= 1, the same bits.  segments=True: also the (n,) uint32 closest-hit plus
+        shadow segments traced per ray."""
+        rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+        n = len(rays)
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+            if len(ids) != n:
+                raise ValueError("radiance_nee: one id per ray")
+        out = np.zeros((n, 3))
+        segs = np.zeros(n, np.uint32) if segments else None
+        p = self._radiance_params(spp, max_depth, seed, first_sample, precision)
+        _check(lib().rtx_radiance_nee(self.h, rays.ctypes.data_as(C.c_void_p),
+                                      None if ids is None else ids.ctypes.data_as(C.c_void_p), n, C.byref(p),
+                                      out.ctypes.data_as(C.c_void_p),
+                                      None if segs is None else segs.ctypes.data_as(C.c_void_p)), "rtx_radiance_nee")
+        return (out, segs) if segments else out
+
+    def radiance_nee_device(self, d_rays, n, d_out, spp, max_depth, seed=1234, first_sample=0, precision="parity",
+                            d_ids=0, d_segments=0, stream=0):
+        """The same on device buffers (rtx_radiance_nee_device), with radiance_device()'s
+        arguments.  Asynchronous."""
+        p = self._radiance_params(spp, max_depth, seed, first_sample, precision)
+        _check(lib().rtx_radiance_nee_device(self.h, C.c_void_p(d_rays), C.c_void_p(d_ids) if d_ids else None, n,
+                                             C.byref(p), C.c_void_p(d_out),
+                                             C.c_void_p(d_segments) if d_segments else None,
+                                             C.c_void_p(stream) if stream else None), "rtx_radiance_nee_device")
+
+    def _nee_frame_args(self, cam, spp, max_depth, seed, precision, tile, stripes):
+        p = RenderParams()
+        p.spp, p.max_depth, p.seed, p.precision = spp, max_depth, seed, PRECISIONS[precision]
+        if stripes is not None:
+            p.stripe_rows, p.stripe_index, p.stripe_count = stripes
+        elif tile is not None:
+            p.x0, p.y0, p.w, p.h = tile
+        n = lib().rtx_render_pixel_count(C.byref(cam), C.byref(p))
+        if n < 0:
+            _check(n, "rtx_render_pixel_count")
+        return p, n
+
+    def render_nee(self, cam, spp, max_depth, seed=1234, precision="parity", tile=None, stripes=None):
+        """A frame with next-event estimation (rtx_render_nee): (rgb (n, 3), segments (n,) uint32)
+        for the pixel subset in subset order, fixed spp; each pixel's samples are radiance_nee() of
+        the camera's own rays keyed by the global pixel index.  Without emitters rgb equals
+        render(adaptive=False, mode="wavefront")'s."""
+        p, n = self._nee_frame_args(cam, spp, max_depth, seed, precision, tile, stripes)
+        rgb = np.zeros((n, 3))
+        segs = np.zeros(n, np.uint32)
+        _check(lib().rtx_render_nee(self.h, C.byref(cam), C.byref(p), rgb.ctypes.data_as(C.c_void_p),
+                                    segs.ctypes.data_as(C.c_void_p)), "rtx_render_nee")
+        return rgb, segs
+
+    def render_nee_device(self, cam, d_rgb, spp, max_depth, seed=1234, precision="parity", tile=None, stripes=None,
+                          d_segments=0, stream=0):
+        """The same into device buffers (rtx_render_nee_device): d_rgb names n x 3 doubles,
+        d_segments n uint32 (0: none).  Asynchronous; returns the subset's pixel count."""
+        p, n = self._nee_frame_args(cam, spp, max_depth, seed, precision, tile, stripes)
+        _check(lib().rtx_render_nee_device(self.h, C.byref(cam), C.byref(p), C.c_void_p(d_rgb),
+                                           C.c_void_p(d_segments) if d_segments else None,
+                                           C.c_void_p(stream) if stream else None), "rtx_render_nee_device")
+        return n
 
     def _ao_args(self, cam, samples, radius, seed, tile, stripes, precision):
         p = RenderParams()
@@ -855,6 +928,57 @@ def direct_samples(scene, points, normals, samples, seed, ids=None, first_sample
     _check(f(scene.h, surfels.ctypes.data_as(C.c_void_p), None if ids is None else ids.ctypes.data_as(C.c_void_p), n,
              C.byref(p), out.ctypes.data_as(C.c_void_p)), "rtx_internal_direct_samples")
     return out
+
+
+def nee_samples(scene, points, normals, samples, seed, depth, ids=None, first_sample=0):
+    """Test hook (rtx_internal_nee_samples, not in rtx.h): direct_samples() on the stream a path of
+    DeviceScene.radiance_nee draws from at a vertex of `depth`, (n, samples, 9)."""
+    surfels = _surfels(points, normals)
+    n = len(surfels)
+    if ids is not None:
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        if len(ids) != n:
+            raise ValueError("nee_samples: one id per point")
+    f = lib().rtx_internal_nee_samples
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RadianceParams), C.c_int32, C.c_void_p]
+    f.restype = C.c_int
+    p = DeviceScene._radiance_params(samples, 0, seed, first_sample, "parity")
+    out = np.zeros((n, samples, 9))
+    _check(f(scene.h, surfels.ctypes.data_as(C.c_void_p), None if ids is None else ids.ctypes.data_as(C.c_void_p), n,
+             C.byref(p), depth, out.ctypes.data_as(C.c_void_p)), "rtx_internal_nee_samples")
+    return out
+
+
+NEE_ELIGIBLE, NEE_TRACED, NEE_VISIBLE, NEE_SUPPRESSED = 1, 2, 4, 8  # rtx_internal_nee_trace's flag bits
+
+
+def nee_trace(scene, rays, spp, max_depth, seed, cap, ids=None, first_sample=0, precision="parity"):
+    """Test hook (rtx_internal_nee_trace, not in rtx.h): the paths DeviceScene.radiance_nee traces
+    for the same arguments, from the device function its kernel runs.  Returns a dict: "p", "n",
+    "w" (n, spp, cap, 3): each segment's vertex point, shading normal and w = throughput x
+    reflectance (zero on a miss; w zero where no term is eligible); "flags" (n, spp, cap) uint32
+    (NEE_* bits); "L_end" (n, spp, 3); "closest", "shadow" (n, spp) uint32 segment counts.
+    Segments a path does not reach are zero."""
+    rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+    n = len(rays)
+    if ids is not None:
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        if len(ids) != n:
+            raise ValueError("nee_trace: one id per ray")
+    f = lib().rtx_internal_nee_trace
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RadianceParams), C.c_int32, C.c_void_p,
+                  C.c_void_p, C.c_void_p, C.c_void_p]
+    f.restype = C.c_int
+    p = DeviceScene._radiance_params(spp, max_depth, seed, first_sample, precision)
+    verts = np.zeros((n, spp, cap, 9))
+    flags = np.zeros((n, spp, cap), np.uint32)
+    ends = np.zeros((n, spp, 3))
+    counts = np.zeros((n, spp, 2), np.uint32)
+    _check(f(scene.h, rays.ctypes.data_as(C.c_void_p), None if ids is None else ids.ctypes.data_as(C.c_void_p), n,
+             C.byref(p), cap, verts.ctypes.data_as(C.c_void_p), flags.ctypes.data_as(C.c_void_p),
+             ends.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p)), "rtx_internal_nee_trace")
+    return {"p": verts[..., 0:3], "n": verts[..., 3:6], "w": verts[..., 6:9], "flags": flags, "L_end": ends,
+            "closest": counts[..., 0], "shadow": counts[..., 1]}
 
 
 def emitter_table(scene):

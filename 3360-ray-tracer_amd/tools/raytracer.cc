@@ -4,7 +4,7 @@
 //             [--mode wavefront|persistent|megakernel] [--precision parity|fast]
 //             [--mk-adaptive MIN:THRESHOLD] [--gpus N]
 //             [--chunks N] [--preview PREFIX] [--checkpoint FILE] [--resume FILE] [--denoise]
-//             [--ao N[,RADIUS]] [--irradiance N[,DEPTH]] [--direct N] > out.ppm
+//             [--ao N[,RADIUS]] [--irradiance N[,DEPTH]] [--direct N] [--nee] > out.ppm
 // --gpus N renders one frame over N GPUs (interleaved row stripes, one host thread per GPU,
 // one gathered framebuffer and P3 output; identical pixels for every N); --devices 0,2,3
 // names the devices (a device may repeat: several streams on one GPU).
@@ -29,6 +29,10 @@
 // first hit, the light arriving straight from the scene's emitters, from N points sampled on the
 // emitters and their shadow segments, keyed by the global pixel; black where the pixel's ray
 // misses) as a P3 PPM through the device encoder; --seed and --precision apply.
+// --nee writes the frame of the light-sampling estimator instead of the plain render
+// (rtx_render_nee: the renderer's own paths with one emitter sample at every diffuse vertex, fixed
+// spp) as a P3 PPM through the device encoder, at the preset's samples and depth (or --spp,
+// --depth); --seed and --precision apply.  Without the flag no output changes.
 // --mk-adaptive selects the AdaptiveSampler (sampler.h:44-82) for --mode megakernel,
 // with max_samples = the preset's (or --spp) samples.
 // Defaults follow main.cc: preset "default" (fallback when unknown), the Cornell box
@@ -60,6 +64,7 @@ int main(int argc, char** argv) {
   bool irr = false;
   int direct_samples = 0;  // --direct
   bool direct = false;
+  bool nee = false;  // --nee
   double ao_radius = 0.0;  // 0: a quarter of the scene's bounding-box diagonal
   std::string preview, checkpoint, resume;
   float mk_thr = 0.0f;
@@ -115,6 +120,7 @@ int main(int argc, char** argv) {
         return 2;
       }
     }
+    else if (a == "--nee") nee = true;
     else if (a == "--devices") {
       const std::string v = next();
       for (size_t p = 0; p < v.size();) {
@@ -240,6 +246,29 @@ int main(int argc, char** argv) {
       std::cout.write(bytes.data(), (std::streamsize)len);
       if (direct) std::clog << "direct: " << direct_samples << " samples, " << n_emitters << " emitters\n";
       else std::clog << "irradiance: " << irr_samples << " samples, depth " << rp.max_depth << "\n";
+    } else if (nee) {
+      integrator::GpuRayIntegrator integ(world.get(), devices.empty() ? 0 : devices[0],
+                                         precision == "fast" ? RTX_PREC_FAST : RTX_PREC_PARITY);
+      const rtx_camera& dc = cam.device();
+      const int W = dc.image_width, H = dc.image_height;
+      const size_t npix = (size_t)W * (size_t)H;
+      rtx_render_params rp{};
+      rp.spp = ns, rp.max_depth = md, rp.seed = seed, rp.precision = integ.precision();
+      std::vector<double> rgb(3 * npix);
+      std::vector<uint32_t> segs(npix);
+      if (rtx_render_nee(integ.device_scene(), &dc, &rp, rgb.data(), segs.data()) != RTX_OK)
+        throw std::runtime_error(std::string("rtx_render_nee: ") + rtx_last_error());
+      int64_t n_emitters = 0;
+      if (rtx_scene_emitters(integ.device_scene(), &n_emitters, nullptr) != RTX_OK)
+        throw std::runtime_error(std::string("rtx_scene_emitters: ") + rtx_last_error());
+      std::string bytes(rtx_p3_max_bytes(W, H), '\0');
+      size_t len = 0;
+      if (rtx_encode_p3(integ.device_scene(), rgb.data(), W, H, bytes.data(), bytes.size(), &len) != RTX_OK)
+        throw std::runtime_error(std::string("rtx_encode_p3: ") + rtx_last_error());
+      std::cout.write(bytes.data(), (std::streamsize)len);
+      uint64_t total = 0;
+      for (uint32_t v : segs) total += v;
+      std::clog << "nee: " << ns << " spp, " << n_emitters << " emitters, " << total << " segments\n";
     } else if (mode == "megakernel") {
       integrator::DefaultSampler fixed_sampler(ns);
       integrator::AdaptiveSampler adaptive_sampler(mk_min, ns, mk_thr);

@@ -595,6 +595,58 @@ int rtx_direct_device(rtx_scene* scene, const rtx_ray* d_surfels, const uint32_t
  * not both. */
 int rtx_scene_emitters(const rtx_scene* scene, int64_t* count, double* area);
 
+/* ---- next-event estimation (DESIGN.md "Next-event estimation") --------------------------------
+ * rtx_radiance and rtx_render find a light only when a path runs into it.  These entry points
+ * trace the same paths and sample the emitters at every diffuse vertex as well: a second, opt-in
+ * estimator of the same radiance with far less variance where lights are small.  Nothing above
+ * changes; results are deterministic in (seed, pixel, sample).
+ * The path of (seed, pixel, sample) is rtx_radiance's path: same closest hits, shading steps,
+ * throughput, Russian roulette and closest-hit segment count (segment d shades from stream d + 1).
+ * On top of it, without multiple importance sampling:
+ *   term: at the hit of segment d, when a Lambertian scattered there, d + 1 < max_depth and the
+ *     emitter table is usable (emitters exist, their area A is finite and > 0), one sample of
+ *     rtx_direct for the surfel (hit point, shading normal), drawn from a Philox stream of its own
+ *     per depth (0xA3000000 + d of the same key), contributes w * (C V): C and V as rtx_direct
+ *     defines them, w = (throughput on arrival at the vertex) * (the Lambertian's reflectance).
+ *     The vertex's roulette does not apply to it.  d + 1 < max_depth mirrors rtx_render's rule that
+ *     a segment at the depth limit returns sky whatever it hit: the plain estimator collects no
+ *     emission there either.
+ *   suppression: a path that ends on an emitter (a hit below the depth limit) right after a vertex
+ *     where a term was eligible contributes 0 there: that light was already sampled.  Emission
+ *     after a metal or dielectric vertex and at segment 0 is collected as before.
+ * A sample's value is the terms added in depth order (from 0) plus the path's end; out_rgb is the
+ * in-order sum of the spp values times 1 / (double)(float)spp, as rtx_radiance resolves.
+ * out_segments (may be NULL): closest-hit segments plus the shadow segments actually traced.
+ * Without emitters, or with max_depth <= 1, every output equals rtx_radiance's bit for bit.
+ * Limit (as rtx_direct): a primitive turned into a light by rtx_scene_update_prims is not in the
+ * emitter table; after a diffuse vertex it is neither sampled nor counted.
+ * Arguments are checked in rtx_radiance's order and with its messages before the scene or a
+ * device is touched, then max_depth > 0x00FFFFFF is RTX_ERR_INVALID (the per-depth streams stay
+ * inside 0xA3000000 .. 0xA3FFFFFF); then n == 0 returns RTX_OK.  One call at a time per scene. */
+/* Host buffers, staged through pinned memory in batches; returns when the outputs are written. */
+int rtx_radiance_nee(rtx_scene* scene, const rtx_ray* rays, const uint32_t* ids, size_t n,
+                     const rtx_radiance_params* params, double* out_rgb, uint32_t* out_segments);
+/* Device buffers; asynchronous on stream (NULL = the scene's stream). */
+int rtx_radiance_nee_device(rtx_scene* scene, const rtx_ray* d_rays, const uint32_t* d_ids, size_t n,
+                            const rtx_radiance_params* params, double* d_out_rgb, uint32_t* d_out_segments,
+                            void* stream);
+/* A frame with that estimator: for every pixel of the subset of params and sample k in [0, spp)
+ * the camera's own ray (the ray rtx_render generates: stream 0 of (seed, global pixel, k)) is the
+ * depth-0 segment of such a path, keyed by the global pixel index.  Read from params: spp (>= 1),
+ * max_depth, seed, precision and the tile / stripe fields; adaptive != 0 is RTX_ERR_INVALID; mode,
+ * flags, min_spp, rel_threshold and samples_per_group are ignored.  out_rgb: 3 doubles per pixel
+ * in subset order, as rtx_render writes them; out_segments (may be NULL): one uint32 per pixel,
+ * all segments of its samples.  Without emitters the frame equals rtx_render's fixed-spp
+ * RTX_MODE_WAVEFRONT frame bit for bit; it equals rtx_radiance_nee fed rtx_render's primary rays
+ * with global pixel ids in every case.  Checks, in order: scene, cam / params, spp, max_depth
+ * (negative, then above 0x00FFFFFF), adaptive, precision, the subset; an empty subset returns
+ * RTX_OK; then out_rgb NULL is RTX_ERR_INVALID.  Host buffers. */
+int rtx_render_nee(rtx_scene* scene, const rtx_camera* cam, const rtx_render_params* params, double* out_rgb,
+                   uint32_t* out_segments);
+/* Device buffers; asynchronous on stream (NULL = the scene's stream). */
+int rtx_render_nee_device(rtx_scene* scene, const rtx_camera* cam, const rtx_render_params* params,
+                          double* d_out_rgb, uint32_t* d_out_segments, void* stream);
+
 enum { RTX_DENOISE_DEMODULATE = 1 }; /* filter colour / max(albedo, 1e-3), multiply back at the end */
 typedef struct {
   int32_t iterations; /* 0..8; iteration k filters 5 x 5 taps at step 2^k; 0 copies the input */
