@@ -101,10 +101,14 @@ __global__ __launch_bounds__(kBlock) void k_emitter_scan(EmitterTable E) {
 // C > 0 (a light that faces away or is seen edge-on, a black light, a NaN).
 // direct_sample_from: the same from `stream` of the key (next-event estimation draws a path
 // vertex's sample from a stream of its own, rtx_nee.h).
-__device__ __forceinline__ bool direct_sample_from(const DScene& S, const EmitterTable& E, uint64_t seed, uint32_t pix,
-                                                   uint32_t smp, uint32_t stream, const rtx_ray& s, V3& o, V3& d,
-                                                   V3& C) {
+// direct_sample_g: direct_sample_from that also gives g, the scalar Le is multiplied by (C = g Le):
+// the ratio of the two solid-angle densities at (x, y), p_bsdf / p_light, which the
+// power-heuristic weights of rtx_nee.h's MIS form are made of.  0 where nothing is traced.
+__device__ __forceinline__ bool direct_sample_g(const DScene& S, const EmitterTable& E, uint64_t seed, uint32_t pix,
+                                                uint32_t smp, uint32_t stream, const rtx_ray& s, V3& o, V3& d, V3& C,
+                                                double& g_out) {
   o = v3(0, 0, 0), d = v3(0, 0, 0), C = v3(0, 0, 0);
+  g_out = 0.0;
   if (E.n <= 0) return false;
   const double A = E.cum[E.n - 1];
   if (!(A > 0.0) || !(A < kInf)) return false;
@@ -160,10 +164,17 @@ __device__ __forceinline__ bool direct_sample_from(const DScene& S, const Emitte
   const V3 w = (1.0 / sqrt(d2)) * seg;
   const double cx = fmax(0.0, dot(normalize(n), w));
   const double cy = fabs(dot(h.normal, w));
-  const V3 c = (((cx * cy) * A) / (kPi * d2)) * Le;
+  const double gs = ((cx * cy) * A) / (kPi * d2);
+  const V3 c = gs * Le;
   if (!(c.x > 0.0 || c.y > 0.0 || c.z > 0.0)) return false;
-  o = x, d = seg, C = c;
+  o = x, d = seg, C = c, g_out = gs;
   return true;
+}
+__device__ __forceinline__ bool direct_sample_from(const DScene& S, const EmitterTable& E, uint64_t seed, uint32_t pix,
+                                                   uint32_t smp, uint32_t stream, const rtx_ray& s, V3& o, V3& d,
+                                                   V3& C) {
+  double gs;
+  return direct_sample_g(S, E, seed, pix, smp, stream, s, o, d, C, gs);
 }
 __device__ __forceinline__ bool direct_sample(const DScene& S, const EmitterTable& E, uint64_t seed, uint32_t pix,
                                               uint32_t smp, const rtx_ray& s, V3& o, V3& d, V3& C) {

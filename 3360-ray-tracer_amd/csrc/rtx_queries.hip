@@ -2,7 +2,8 @@
 // closest hit (rtx_intersect*), any hit and the AO pass (rtx_occluded*, rtx_ao*), first-hit AOVs
 // (rtx_aov*), radiance, irradiance and direct lighting on caller-supplied rays and surfels
 // (rtx_radiance*, rtx_irradiance*, rtx_direct*, rtx_scene_emitters), the light-sampling estimator
-// on rays and on the camera's own frame (rtx_radiance_nee*, rtx_render_nee*), with their test hooks.
+// on rays and on the camera's own frame (rtx_radiance_nee*, rtx_render_nee*) and its power-heuristic
+// form (rtx_radiance_mis*, rtx_render_mis*), with their test hooks.
 // Scenes, films and the frame renderer are rtx_capi.hip's; the two share rtx_host.h.  Every query
 // picks its walk with with_walk (fast only with a fast tree, the scene's stack size).
 #include <atomic>
@@ -75,8 +76,8 @@ int ao_check(const rtx_scene* sc, const rtx_camera* cam, const rtx_render_params
 std::atomic<int64_t> g_radiance_chunk{0};
 // what a chunk's slots hold (radiance_on): a path from a caller's ray, a path from a surfel's
 // hemisphere sample, a surfel's emitter sample, or a path with next-event estimation (from a
-// caller's ray, or from the camera when radiance_on is given one)
-enum SlotKind { kSlotRadiance = 0, kSlotIrradiance = 1, kSlotDirect = 2, kSlotNee = 3 };
+// caller's ray, or from the camera when radiance_on is given one), plain or with MIS weights
+enum SlotKind { kSlotRadiance = 0, kSlotIrradiance = 1, kSlotDirect = 2, kSlotNee = 3, kSlotMis = 4 };
 // the checks rtx_radiance*, rtx_irradiance*, rtx_direct* and their test hooks share, in the documented order
 int radiance_check(const rtx_scene* sc, const rtx_radiance_params* prm, const void* rays, const void* out) {
   if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
@@ -91,8 +92,10 @@ int radiance_check(const rtx_scene* sc, const rtx_radiance_params* prm, const vo
   return RTX_OK;
 }
 // next-event estimation: the vertex of segment d draws from stream kRngStreamNee + d, d < max_depth
-int nee_depth_check(int32_t max_depth) {
-  if (max_depth > 0x00FFFFFF) return fail(RTX_ERR_INVALID, "nee: max_depth above 16777215 (0x00FFFFFF)");
+int nee_depth_check(int32_t max_depth, bool mis = false) {
+  if (max_depth > 0x00FFFFFF)
+    return fail(RTX_ERR_INVALID, mis ? "mis: max_depth above 16777215 (0x00FFFFFF)"
+                                     : "nee: max_depth above 16777215 (0x00FFFFFF)");
   return RTX_OK;
 }
 // n > 0 rays on device buffers, in chunks of at most `cap` slots (ray x sample): whole rays per
@@ -102,7 +105,8 @@ int nee_depth_check(int32_t max_depth) {
 // surfels and the slots are k_irradiance's (rtx_irradiance*) or k_direct's (rtx_direct*: a
 // slot's "segments" are its visibility, 0 or 1); the chunking, the scratch and the sum are the same.
 // kSlotNee: k_radiance_nee's slots, or with `cam` k_render_nee's: the "rays" are then the n pixels
-// of the camera's subset in subset order (d_rays and d_ids are not read).
+// of the camera's subset in subset order (d_rays and d_ids are not read).  kSlotMis: the same with
+// k_radiance_mis / k_render_mis.
 int radiance_on(rtx_scene* sc, const rtx_ray* d_rays, const uint32_t* d_ids, uint64_t id_base, int64_t n,
                 const rtx_radiance_params* prm, double* d_out, uint32_t* d_segs, hipStream_t s,
                 SlotKind what = kSlotRadiance, const NeeCamera* cam = nullptr) {
@@ -137,6 +141,10 @@ int radiance_on(rtx_scene* sc, const rtx_ray* d_rays, const uint32_t* d_ids, uin
             if (cam) rc = launch_1d(k_render_nee<w.stack, w.fast>, A.slots, lds, s, sc->S, emitter_table(sc), A, *cam);
             else rc = launch_1d(k_radiance_nee<w.stack, w.fast>, A.slots, lds, s, sc->S, emitter_table(sc), A);
             break;
+          case kSlotMis:
+            if (cam) rc = launch_1d(k_render_mis<w.stack, w.fast>, A.slots, lds, s, sc->S, emitter_table(sc), A, *cam);
+            else rc = launch_1d(k_radiance_mis<w.stack, w.fast>, A.slots, lds, s, sc->S, emitter_table(sc), A);
+            break;
           default: rc = launch_1d(k_radiance<w.stack, w.fast>, A.slots, lds, s, sc->S, A);
         }
         if (rc) return rc;
@@ -157,7 +165,7 @@ int radiance_host(rtx_scene* sc, const rtx_ray* rays, const uint32_t* ids, size_
                   double* out_rgb, uint32_t* out_segments, SlotKind what) {
   int rc;
   if ((rc = radiance_check(sc, prm, rays, out_rgb))) return rc;
-  if (what == kSlotNee && (rc = nee_depth_check(prm->max_depth))) return rc;
+  if ((what == kSlotNee || what == kSlotMis) && (rc = nee_depth_check(prm->max_depth, what == kSlotMis))) return rc;
   if (n == 0) return RTX_OK;
   HIPC(hipSetDevice(sc->device));
   const size_t m = std::min(n, kRadianceHostRays);
@@ -196,7 +204,7 @@ int radiance_device(rtx_scene* sc, const rtx_ray* d_rays, const uint32_t* d_ids,
                     SlotKind what) {
   int rc;
   if ((rc = radiance_check(sc, prm, d_rays, d_out_rgb))) return rc;
-  if (what == kSlotNee && (rc = nee_depth_check(prm->max_depth))) return rc;
+  if ((what == kSlotNee || what == kSlotMis) && (rc = nee_depth_check(prm->max_depth, what == kSlotMis))) return rc;
   if (n == 0) return RTX_OK;
   HIPC(hipSetDevice(sc->device));
   return radiance_on(sc, d_rays, d_ids, 0, (int64_t)n, prm, d_out_rgb, d_out_segments,
@@ -228,25 +236,117 @@ int surfel_samples(rtx_scene* sc, const rtx_ray* surfels, const uint32_t* ids, s
   return RTX_OK;
 }
 // ---- frames with next-event estimation (rtx_nee.h) ----
-// the checks rtx_render_nee and rtx_render_nee_device share, in the documented order; *npix:
-// pixels of the subset; rp: the render params read as the radiance family reads its own
+// the checks rtx_render_nee / rtx_render_mis and their _device forms share, in the documented
+// order; *npix: pixels of the subset; rp: the render params read as the radiance family reads its
+// own; mis: the messages say "mis" where the NEE family's say "nee"
 int render_nee_check(const rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, NeeCamera& nc,
-                     int64_t* npix, rtx_radiance_params& rp) {
+                     int64_t* npix, rtx_radiance_params& rp, bool mis = false) {
   if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
   if (!cam || !prm) return fail(RTX_ERR_INVALID, "NULL argument");
-  if (prm->spp < 1) return fail(RTX_ERR_INVALID, "render nee: spp must be at least 1");
+  if (prm->spp < 1)
+    return fail(RTX_ERR_INVALID, mis ? "render mis: spp must be at least 1" : "render nee: spp must be at least 1");
   if (prm->max_depth < 0) return fail(RTX_ERR_INVALID, "negative max_depth");
   int rc;
-  if ((rc = nee_depth_check(prm->max_depth))) return rc;
-  if (prm->adaptive != 0) return fail(RTX_ERR_INVALID, "render nee: adaptive sampling is not supported (fixed spp only)");
+  if ((rc = nee_depth_check(prm->max_depth, mis))) return rc;
+  if (prm->adaptive != 0)
+    return fail(RTX_ERR_INVALID, mis ? "render mis: adaptive sampling is not supported (fixed spp only)"
+                                     : "render nee: adaptive sampling is not supported (fixed spp only)");
   if (prm->precision != RTX_PREC_PARITY && prm->precision != RTX_PREC_FAST)
-    return fail(RTX_ERR_INVALID, "render nee: bad precision");
+    return fail(RTX_ERR_INVALID, mis ? "render mis: bad precision" : "render nee: bad precision");
   std::string err;
   *npix = subset_pixels(cam, prm, nc.map, err);
   if (*npix < 0) return fail(RTX_ERR_INVALID, err);
   nc.cam = *cam;
   rp.spp = prm->spp, rp.max_depth = prm->max_depth, rp.first_sample = 0, rp.precision = prm->precision;
   rp.seed = prm->seed;
+  return RTX_OK;
+}
+// the frame entry points of the two families (what: kSlotNee or kSlotMis)
+int render_nee_device(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, double* d_out_rgb,
+                      uint32_t* d_out_segments, void* stream, SlotKind what) {
+  NeeCamera nc;
+  int64_t npix;
+  rtx_radiance_params rp{};
+  int rc;
+  if ((rc = render_nee_check(sc, cam, prm, nc, &npix, rp, what == kSlotMis))) return rc;
+  if (npix == 0) return RTX_OK;
+  if (!d_out_rgb) return fail(RTX_ERR_INVALID, "NULL buffer");
+  HIPC(hipSetDevice(sc->device));
+  return radiance_on(sc, nullptr, nullptr, 0, npix, &rp, d_out_rgb, d_out_segments,
+                     stream ? (hipStream_t)stream : sc->stream, what, &nc);
+}
+int render_nee_host(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, double* out_rgb,
+                    uint32_t* out_segments, SlotKind what) {
+  NeeCamera nc;
+  int64_t npix;
+  rtx_radiance_params rp{};
+  int rc;
+  if ((rc = render_nee_check(sc, cam, prm, nc, &npix, rp, what == kSlotMis))) return rc;
+  if (npix == 0) return RTX_OK;
+  if (!out_rgb) return fail(RTX_ERR_INVALID, "NULL buffer");
+  HIPC(hipSetDevice(sc->device));
+  if ((rc = sc->rad_out.reserve((size_t)npix * 3 * sizeof(double)))) return rc;
+  if ((rc = sc->rad_oseg.reserve((size_t)npix * sizeof(uint32_t)))) return rc;
+  if ((rc = radiance_on(sc, nullptr, nullptr, 0, npix, &rp, sc->rad_out.as<double>(), sc->rad_oseg.as<uint32_t>(),
+                        sc->stream, what, &nc)))
+    return rc;
+  HIPC(hipMemcpyAsync(out_rgb, sc->rad_out.p, (size_t)npix * 3 * sizeof(double), hipMemcpyDeviceToHost, sc->stream));
+  if (out_segments)
+    HIPC(hipMemcpyAsync(out_segments, sc->rad_oseg.p, (size_t)npix * sizeof(uint32_t), hipMemcpyDeviceToHost, sc->stream));
+  HIPC(hipStreamSynchronize(sc->stream));
+  return RTX_OK;
+}
+// What rtx_internal_nee_trace and rtx_internal_mis_trace share (per: doubles per recorded segment,
+// 9 or 11; the MIS form launches k_mis_trace and says "mis" in its messages).
+int path_trace_hook(rtx_scene* sc, const rtx_ray* rays, const uint32_t* ids, size_t n, const rtx_radiance_params* prm,
+                    int32_t cap, double* verts, uint32_t* flags, double* ends, uint32_t* counts, bool mis) {
+  const size_t per = mis ? 11 : 9;
+  int rc;
+  if ((rc = radiance_check(sc, prm, rays, verts))) return rc;
+  if ((rc = nee_depth_check(prm->max_depth, mis))) return rc;
+  if (!flags || !ends || !counts) return fail(RTX_ERR_INVALID, "NULL buffer");
+  if (cap < 1 || cap > 4096)
+    return fail(RTX_ERR_INVALID, mis ? "mis trace: cap outside 1..4096" : "nee trace: cap outside 1..4096");
+  if (n == 0) return RTX_OK;
+  if (n > ((size_t)1 << 20) || (int64_t)n * prm->spp * cap > ((int64_t)1 << 22))
+    return fail(RTX_ERR_INVALID,
+                mis ? "mis trace: too many records for one call" : "nee trace: too many records for one call");
+  HIPC(hipSetDevice(sc->device));
+  const size_t nslots = n * (size_t)prm->spp, nrec = nslots * (size_t)cap;
+  // doubles: verts | ends (rad_L); words: flags | counts (rad_segs)
+  const size_t b_verts = nrec * per * sizeof(double), b_ends = nslots * 3 * sizeof(double);
+  const size_t b_flags = nrec * sizeof(uint32_t), b_counts = nslots * 2 * sizeof(uint32_t);
+  if ((rc = sc->rays.reserve(n * sizeof(rtx_ray)))) return rc;
+  if ((rc = sc->rad_L.reserve(b_verts + b_ends))) return rc;
+  if ((rc = sc->rad_segs.reserve(b_flags + b_counts))) return rc;
+  if (ids && (rc = sc->rad_ids.reserve(n * sizeof(uint32_t)))) return rc;
+  hipStream_t s = sc->stream;
+  HIPC(hipMemcpyAsync(sc->rays.p, rays, n * sizeof(rtx_ray), hipMemcpyHostToDevice, s));
+  if (ids) HIPC(hipMemcpyAsync(sc->rad_ids.p, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  HIPC(hipMemsetAsync(sc->rad_L.p, 0, b_verts + b_ends, s));
+  HIPC(hipMemsetAsync(sc->rad_segs.p, 0, b_flags + b_counts, s));
+  double* const d_verts = sc->rad_L.as<double>();
+  double* const d_ends = d_verts + nrec * per;
+  uint32_t* const d_flags = sc->rad_segs.as<uint32_t>();
+  uint32_t* const d_counts = d_flags + nrec;
+  RadianceChunk A;
+  A.rays = sc->rays.as<rtx_ray>(), A.ids = ids ? sc->rad_ids.as<uint32_t>() : nullptr, A.ray0 = 0, A.id_base = 0;
+  A.slots = (uint32_t)nslots, A.K = (uint32_t)prm->spp;
+  A.s0 = prm->first_sample, A.max_depth = prm->max_depth, A.seed = prm->seed;
+  A.L = nullptr, A.segs = nullptr;  // (not written by k_nee_trace / k_mis_trace)
+  if ((rc = with_walk(sc, prm->precision, [&](auto w) {
+         if (mis)
+           return launch_1d(k_mis_trace<w.stack, w.fast>, (int64_t)nslots, stack_lds_bytes(w.stack), s, sc->S,
+                            emitter_table(sc), A, cap, d_verts, d_flags, d_ends, d_counts);
+         return launch_1d(k_nee_trace<w.stack, w.fast>, (int64_t)nslots, stack_lds_bytes(w.stack), s, sc->S,
+                          emitter_table(sc), A, cap, d_verts, d_flags, d_ends, d_counts);
+       })))
+    return rc;
+  HIPC(hipMemcpyAsync(verts, d_verts, b_verts, hipMemcpyDeviceToHost, s));
+  HIPC(hipMemcpyAsync(ends, d_ends, b_ends, hipMemcpyDeviceToHost, s));
+  HIPC(hipMemcpyAsync(flags, d_flags, b_flags, hipMemcpyDeviceToHost, s));
+  HIPC(hipMemcpyAsync(counts, d_counts, b_counts, hipMemcpyDeviceToHost, s));
+  HIPC(hipStreamSynchronize(s));
   return RTX_OK;
 }
 }  // namespace
@@ -502,38 +602,30 @@ int rtx_radiance_nee(rtx_scene* sc, const rtx_ray* rays, const uint32_t* ids, si
 
 int rtx_render_nee_device(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, double* d_out_rgb,
                           uint32_t* d_out_segments, void* stream) {
-  NeeCamera nc;
-  int64_t npix;
-  rtx_radiance_params rp{};
-  int rc;
-  if ((rc = render_nee_check(sc, cam, prm, nc, &npix, rp))) return rc;
-  if (npix == 0) return RTX_OK;
-  if (!d_out_rgb) return fail(RTX_ERR_INVALID, "NULL buffer");
-  HIPC(hipSetDevice(sc->device));
-  return radiance_on(sc, nullptr, nullptr, 0, npix, &rp, d_out_rgb, d_out_segments,
-                     stream ? (hipStream_t)stream : sc->stream, kSlotNee, &nc);
+  return render_nee_device(sc, cam, prm, d_out_rgb, d_out_segments, stream, kSlotNee);
 }
-
 int rtx_render_nee(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, double* out_rgb,
                    uint32_t* out_segments) {
-  NeeCamera nc;
-  int64_t npix;
-  rtx_radiance_params rp{};
-  int rc;
-  if ((rc = render_nee_check(sc, cam, prm, nc, &npix, rp))) return rc;
-  if (npix == 0) return RTX_OK;
-  if (!out_rgb) return fail(RTX_ERR_INVALID, "NULL buffer");
-  HIPC(hipSetDevice(sc->device));
-  if ((rc = sc->rad_out.reserve((size_t)npix * 3 * sizeof(double)))) return rc;
-  if ((rc = sc->rad_oseg.reserve((size_t)npix * sizeof(uint32_t)))) return rc;
-  if ((rc = radiance_on(sc, nullptr, nullptr, 0, npix, &rp, sc->rad_out.as<double>(), sc->rad_oseg.as<uint32_t>(),
-                        sc->stream, kSlotNee, &nc)))
-    return rc;
-  HIPC(hipMemcpyAsync(out_rgb, sc->rad_out.p, (size_t)npix * 3 * sizeof(double), hipMemcpyDeviceToHost, sc->stream));
-  if (out_segments)
-    HIPC(hipMemcpyAsync(out_segments, sc->rad_oseg.p, (size_t)npix * sizeof(uint32_t), hipMemcpyDeviceToHost, sc->stream));
-  HIPC(hipStreamSynchronize(sc->stream));
-  return RTX_OK;
+  return render_nee_host(sc, cam, prm, out_rgb, out_segments, kSlotNee);
+}
+
+// ---- the power-heuristic form (rtx_nee.h, MIS): the NEE family's checks, chunks and staging ----
+int rtx_radiance_mis_device(rtx_scene* sc, const rtx_ray* d_rays, const uint32_t* d_ids, size_t n,
+                            const rtx_radiance_params* prm, double* d_out_rgb, uint32_t* d_out_segments,
+                            void* stream) {
+  return radiance_device(sc, d_rays, d_ids, n, prm, d_out_rgb, d_out_segments, stream, kSlotMis);
+}
+int rtx_radiance_mis(rtx_scene* sc, const rtx_ray* rays, const uint32_t* ids, size_t n, const rtx_radiance_params* prm,
+                     double* out_rgb, uint32_t* out_segments) {
+  return radiance_host(sc, rays, ids, n, prm, out_rgb, out_segments, kSlotMis);
+}
+int rtx_render_mis_device(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, double* d_out_rgb,
+                          uint32_t* d_out_segments, void* stream) {
+  return render_nee_device(sc, cam, prm, d_out_rgb, d_out_segments, stream, kSlotMis);
+}
+int rtx_render_mis(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, double* out_rgb,
+                   uint32_t* out_segments) {
+  return render_nee_host(sc, cam, prm, out_rgb, out_segments, kSlotMis);
 }
 
 // Test hook (not in rtx.h): rtx_internal_direct_samples on stream kRngStreamNee + depth, the
@@ -560,48 +652,18 @@ int rtx_internal_nee_samples(rtx_scene* sc, const rtx_ray* surfels, const uint32
 int rtx_internal_nee_trace(rtx_scene* sc, const rtx_ray* rays, const uint32_t* ids, size_t n,
                            const rtx_radiance_params* prm, int32_t cap, double* verts, uint32_t* flags, double* ends,
                            uint32_t* counts) {
-  int rc;
-  if ((rc = radiance_check(sc, prm, rays, verts))) return rc;
-  if ((rc = nee_depth_check(prm->max_depth))) return rc;
-  if (!flags || !ends || !counts) return fail(RTX_ERR_INVALID, "NULL buffer");
-  if (cap < 1 || cap > 4096) return fail(RTX_ERR_INVALID, "nee trace: cap outside 1..4096");
-  if (n == 0) return RTX_OK;
-  if (n > ((size_t)1 << 20) || (int64_t)n * prm->spp * cap > ((int64_t)1 << 22))
-    return fail(RTX_ERR_INVALID, "nee trace: too many records for one call");
-  HIPC(hipSetDevice(sc->device));
-  const size_t nslots = n * (size_t)prm->spp, nrec = nslots * (size_t)cap;
-  // doubles: verts | ends (rad_L); words: flags | counts (rad_segs)
-  const size_t b_verts = nrec * 9 * sizeof(double), b_ends = nslots * 3 * sizeof(double);
-  const size_t b_flags = nrec * sizeof(uint32_t), b_counts = nslots * 2 * sizeof(uint32_t);
-  if ((rc = sc->rays.reserve(n * sizeof(rtx_ray)))) return rc;
-  if ((rc = sc->rad_L.reserve(b_verts + b_ends))) return rc;
-  if ((rc = sc->rad_segs.reserve(b_flags + b_counts))) return rc;
-  if (ids && (rc = sc->rad_ids.reserve(n * sizeof(uint32_t)))) return rc;
-  hipStream_t s = sc->stream;
-  HIPC(hipMemcpyAsync(sc->rays.p, rays, n * sizeof(rtx_ray), hipMemcpyHostToDevice, s));
-  if (ids) HIPC(hipMemcpyAsync(sc->rad_ids.p, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-  HIPC(hipMemsetAsync(sc->rad_L.p, 0, b_verts + b_ends, s));
-  HIPC(hipMemsetAsync(sc->rad_segs.p, 0, b_flags + b_counts, s));
-  double* const d_verts = sc->rad_L.as<double>();
-  double* const d_ends = d_verts + nrec * 9;
-  uint32_t* const d_flags = sc->rad_segs.as<uint32_t>();
-  uint32_t* const d_counts = d_flags + nrec;
-  RadianceChunk A;
-  A.rays = sc->rays.as<rtx_ray>(), A.ids = ids ? sc->rad_ids.as<uint32_t>() : nullptr, A.ray0 = 0, A.id_base = 0;
-  A.slots = (uint32_t)nslots, A.K = (uint32_t)prm->spp;
-  A.s0 = prm->first_sample, A.max_depth = prm->max_depth, A.seed = prm->seed;
-  A.L = nullptr, A.segs = nullptr;  // (not written by k_nee_trace)
-  if ((rc = with_walk(sc, prm->precision, [&](auto w) {
-         return launch_1d(k_nee_trace<w.stack, w.fast>, (int64_t)nslots, stack_lds_bytes(w.stack), s, sc->S,
-                          emitter_table(sc), A, cap, d_verts, d_flags, d_ends, d_counts);
-       })))
-    return rc;
-  HIPC(hipMemcpyAsync(verts, d_verts, b_verts, hipMemcpyDeviceToHost, s));
-  HIPC(hipMemcpyAsync(ends, d_ends, b_ends, hipMemcpyDeviceToHost, s));
-  HIPC(hipMemcpyAsync(flags, d_flags, b_flags, hipMemcpyDeviceToHost, s));
-  HIPC(hipMemcpyAsync(counts, d_counts, b_counts, hipMemcpyDeviceToHost, s));
-  HIPC(hipStreamSynchronize(s));
-  return RTX_OK;
+  return path_trace_hook(sc, rays, ids, n, prm, cap, verts, flags, ends, counts, false);
+}
+
+// Test hook (not in rtx.h): rtx_internal_nee_trace for the paths of rtx_radiance_mis (k_mis_trace,
+// rtx_nee.h).  verts holds 11 doubles per slot and segment: the nine of rtx_internal_nee_trace,
+// then g of the vertex's light sample (0 where none was traceable) and the gb applied to the
+// segment's emission (0 where none applied).  Flag 8 is never set; 16: the path ended here on an
+// emitter of the table and its emission was weighted with gb.  Messages say "mis".
+int rtx_internal_mis_trace(rtx_scene* sc, const rtx_ray* rays, const uint32_t* ids, size_t n,
+                           const rtx_radiance_params* prm, int32_t cap, double* verts, uint32_t* flags, double* ends,
+                           uint32_t* counts) {
+  return path_trace_hook(sc, rays, ids, n, prm, cap, verts, flags, ends, counts, true);
 }
 
 // Test hook (not in rtx.h): one shading step per case (rtx_shade_steps.h), n ShadeCase in and n

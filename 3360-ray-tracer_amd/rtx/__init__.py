@@ -146,7 +146,8 @@ EXPORTS = ["rtx_abi_version", "rtx_last_error", "rtx_device_count", "rtx_scene_c
            "rtx_scene_update_geometry_device", "rtx_scene_epoch", "rtx_bvh_refit_host", "rtx_film_reset",
            "rtx_occluded", "rtx_occluded_device", "rtx_ao", "rtx_ao_device", "rtx_radiance", "rtx_radiance_device",
            "rtx_irradiance", "rtx_irradiance_device", "rtx_direct", "rtx_direct_device", "rtx_scene_emitters",
-           "rtx_radiance_nee", "rtx_radiance_nee_device", "rtx_render_nee", "rtx_render_nee_device"]
+           "rtx_radiance_nee", "rtx_radiance_nee_device", "rtx_render_nee", "rtx_render_nee_device",
+           "rtx_radiance_mis", "rtx_radiance_mis_device", "rtx_render_mis", "rtx_render_mis_device"]
 
 _lib = None
 
@@ -229,6 +230,10 @@ def lib():
             "rtx_radiance_nee_device": ([vp, vp, vp, sz, C.POINTER(RadianceParams), vp, vp, vp], C.c_int),
             "rtx_render_nee": ([vp, C.POINTER(Camera), C.POINTER(RenderParams), vp, vp], C.c_int),
             "rtx_render_nee_device": ([vp, C.POINTER(Camera), C.POINTER(RenderParams), vp, vp, vp], C.c_int),
+            "rtx_radiance_mis": ([vp, vp, vp, sz, C.POINTER(RadianceParams), vp, vp], C.c_int),
+            "rtx_radiance_mis_device": ([vp, vp, vp, sz, C.POINTER(RadianceParams), vp, vp, vp], C.c_int),
+            "rtx_render_mis": ([vp, C.POINTER(Camera), C.POINTER(RenderParams), vp, vp], C.c_int),
+            "rtx_render_mis_device": ([vp, C.POINTER(Camera), C.POINTER(RenderParams), vp, vp, vp], C.c_int),
         }
         for name, (args, res) in sig.items():
             f = getattr(L, name)
@@ -533,19 +538,24 @@ class DeviceScene:
         as radiance() with far less variance where lights are small; without emitters, or with
         max_depth <= 1, the same bits.  segments=True: also the (n,) uint32 closest-hit plus
         shadow segments traced per ray."""
+        return self._radiance_sampled("nee", rays, spp, max_depth, seed, ids, first_sample, precision, segments)
+
+    def _radiance_sampled(self, family, rays, spp, max_depth, seed, ids, first_sample, precision, segments):
+        """radiance_nee() / radiance_mis(): rtx_radiance_<family> on host arrays."""
         rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
         n = len(rays)
         if ids is not None:
             ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
             if len(ids) != n:
-                raise ValueError("radiance_nee: one id per ray")
+                raise ValueError("radiance_%s: one id per ray" % family)
         out = np.zeros((n, 3))
         segs = np.zeros(n, np.uint32) if segments else None
         p = self._radiance_params(spp, max_depth, seed, first_sample, precision)
-        _check(lib().rtx_radiance_nee(self.h, rays.ctypes.data_as(C.c_void_p),
-                                      None if ids is None else ids.ctypes.data_as(C.c_void_p), n, C.byref(p),
-                                      out.ctypes.data_as(C.c_void_p),
-                                      None if segs is None else segs.ctypes.data_as(C.c_void_p)), "rtx_radiance_nee")
+        name = "rtx_radiance_" + family
+        _check(getattr(lib(), name)(self.h, rays.ctypes.data_as(C.c_void_p),
+                                    None if ids is None else ids.ctypes.data_as(C.c_void_p), n, C.byref(p),
+                                    out.ctypes.data_as(C.c_void_p),
+                                    None if segs is None else segs.ctypes.data_as(C.c_void_p)), name)
         return (out, segs) if segments else out
 
     def radiance_nee_device(self, d_rays, n, d_out, spp, max_depth, seed=1234, first_sample=0, precision="parity",
@@ -590,6 +600,48 @@ class DeviceScene:
         _check(lib().rtx_render_nee_device(self.h, C.byref(cam), C.byref(p), C.c_void_p(d_rgb),
                                            C.c_void_p(d_segments) if d_segments else None,
                                            C.c_void_p(stream) if stream else None), "rtx_render_nee_device")
+        return n
+
+    def radiance_mis(self, rays, spp, max_depth, seed=1234, ids=None, first_sample=0, precision="parity",
+                     segments=False):
+        """Radiance query with multiple importance sampling (rtx_radiance_mis): radiance_nee()'s
+        arguments, paths, emitter samples and segment counts; each emitter sample is weighted by
+        the power heuristic's 1 / (1 + g^2) (g: the ratio of the BSDF's density to the light
+        sampler's at that pair of points), and an emitter hit right after such a vertex counts with
+        the complementary weight instead of 0 (with weight 1 for a light the emitter table does
+        not hold).  The same expectation as radiance(), without radiance_nee()'s fireflies where a
+        surface comes close to a light; without emitters, or with max_depth <= 1, the same bits."""
+        return self._radiance_sampled("mis", rays, spp, max_depth, seed, ids, first_sample, precision, segments)
+
+    def radiance_mis_device(self, d_rays, n, d_out, spp, max_depth, seed=1234, first_sample=0, precision="parity",
+                            d_ids=0, d_segments=0, stream=0):
+        """The same on device buffers (rtx_radiance_mis_device), with radiance_device()'s
+        arguments.  Asynchronous."""
+        p = self._radiance_params(spp, max_depth, seed, first_sample, precision)
+        _check(lib().rtx_radiance_mis_device(self.h, C.c_void_p(d_rays), C.c_void_p(d_ids) if d_ids else None, n,
+                                             C.byref(p), C.c_void_p(d_out),
+                                             C.c_void_p(d_segments) if d_segments else None,
+                                             C.c_void_p(stream) if stream else None), "rtx_radiance_mis_device")
+
+    def render_mis(self, cam, spp, max_depth, seed=1234, precision="parity", tile=None, stripes=None):
+        """A frame with multiple importance sampling (rtx_render_mis): render_nee()'s arguments and
+        outputs; each pixel's samples are radiance_mis() of the camera's own rays keyed by the
+        global pixel index."""
+        p, n = self._nee_frame_args(cam, spp, max_depth, seed, precision, tile, stripes)
+        rgb = np.zeros((n, 3))
+        segs = np.zeros(n, np.uint32)
+        _check(lib().rtx_render_mis(self.h, C.byref(cam), C.byref(p), rgb.ctypes.data_as(C.c_void_p),
+                                    segs.ctypes.data_as(C.c_void_p)), "rtx_render_mis")
+        return rgb, segs
+
+    def render_mis_device(self, cam, d_rgb, spp, max_depth, seed=1234, precision="parity", tile=None, stripes=None,
+                          d_segments=0, stream=0):
+        """The same into device buffers (rtx_render_mis_device), with render_nee_device()'s
+        arguments.  Asynchronous; returns the subset's pixel count."""
+        p, n = self._nee_frame_args(cam, spp, max_depth, seed, precision, tile, stripes)
+        _check(lib().rtx_render_mis_device(self.h, C.byref(cam), C.byref(p), C.c_void_p(d_rgb),
+                                           C.c_void_p(d_segments) if d_segments else None,
+                                           C.c_void_p(stream) if stream else None), "rtx_render_mis_device")
         return n
 
     def _ao_args(self, cam, samples, radius, seed, tile, stripes, precision):
@@ -979,6 +1031,37 @@ def nee_trace(scene, rays, spp, max_depth, seed, cap, ids=None, first_sample=0, 
              ends.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p)), "rtx_internal_nee_trace")
     return {"p": verts[..., 0:3], "n": verts[..., 3:6], "w": verts[..., 6:9], "flags": flags, "L_end": ends,
             "closest": counts[..., 0], "shadow": counts[..., 1]}
+
+
+MIS_WEIGHTED = 16  # rtx_internal_mis_trace's own flag bit (NEE_SUPPRESSED is never set there)
+
+
+def mis_trace(scene, rays, spp, max_depth, seed, cap, ids=None, first_sample=0, precision="parity"):
+    """Test hook (rtx_internal_mis_trace, not in rtx.h): nee_trace() for the paths of
+    DeviceScene.radiance_mis.  The same dict with two more entries: "g" (n, spp, cap), the scalar of
+    each vertex's light sample (0 where none was traceable), and "gb" (n, spp, cap), the gb applied
+    to the emission of the segment that ended the path there (0 where none applied).  flags:
+    NEE_ELIGIBLE / NEE_TRACED / NEE_VISIBLE and MIS_WEIGHTED."""
+    rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+    n = len(rays)
+    if ids is not None:
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        if len(ids) != n:
+            raise ValueError("mis_trace: one id per ray")
+    f = lib().rtx_internal_mis_trace
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RadianceParams), C.c_int32, C.c_void_p,
+                  C.c_void_p, C.c_void_p, C.c_void_p]
+    f.restype = C.c_int
+    p = DeviceScene._radiance_params(spp, max_depth, seed, first_sample, precision)
+    verts = np.zeros((n, spp, cap, 11))
+    flags = np.zeros((n, spp, cap), np.uint32)
+    ends = np.zeros((n, spp, 3))
+    counts = np.zeros((n, spp, 2), np.uint32)
+    _check(f(scene.h, rays.ctypes.data_as(C.c_void_p), None if ids is None else ids.ctypes.data_as(C.c_void_p), n,
+             C.byref(p), cap, verts.ctypes.data_as(C.c_void_p), flags.ctypes.data_as(C.c_void_p),
+             ends.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p)), "rtx_internal_mis_trace")
+    return {"p": verts[..., 0:3], "n": verts[..., 3:6], "w": verts[..., 6:9], "g": verts[..., 9], "gb": verts[..., 10],
+            "flags": flags, "L_end": ends, "closest": counts[..., 0], "shadow": counts[..., 1]}
 
 
 def emitter_table(scene):

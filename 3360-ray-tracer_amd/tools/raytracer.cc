@@ -4,7 +4,7 @@
 //             [--mode wavefront|persistent|megakernel] [--precision parity|fast]
 //             [--mk-adaptive MIN:THRESHOLD] [--gpus N]
 //             [--chunks N] [--preview PREFIX] [--checkpoint FILE] [--resume FILE] [--denoise]
-//             [--ao N[,RADIUS]] [--irradiance N[,DEPTH]] [--direct N] [--nee] > out.ppm
+//             [--ao N[,RADIUS]] [--irradiance N[,DEPTH]] [--direct N] [--nee | --mis] > out.ppm
 // --gpus N renders one frame over N GPUs (interleaved row stripes, one host thread per GPU,
 // one gathered framebuffer and P3 output; identical pixels for every N); --devices 0,2,3
 // names the devices (a device may repeat: several streams on one GPU).
@@ -33,6 +33,9 @@
 // (rtx_render_nee: the renderer's own paths with one emitter sample at every diffuse vertex, fixed
 // spp) as a P3 PPM through the device encoder, at the preset's samples and depth (or --spp,
 // --depth); --seed and --precision apply.  Without the flag no output changes.
+// --mis writes the frame of the combined estimator in the same way (rtx_render_mis: the same paths
+// and emitter samples, the two strategies weighted with the power heuristic, so a lamp close to a
+// wall leaves no fireflies); --nee and --mis together is an error.
 // --mk-adaptive selects the AdaptiveSampler (sampler.h:44-82) for --mode megakernel,
 // with max_samples = the preset's (or --spp) samples.
 // Defaults follow main.cc: preset "default" (fallback when unknown), the Cornell box
@@ -65,6 +68,7 @@ int main(int argc, char** argv) {
   int direct_samples = 0;  // --direct
   bool direct = false;
   bool nee = false;  // --nee
+  bool mis = false;  // --mis
   double ao_radius = 0.0;  // 0: a quarter of the scene's bounding-box diagonal
   std::string preview, checkpoint, resume;
   float mk_thr = 0.0f;
@@ -121,6 +125,7 @@ int main(int argc, char** argv) {
       }
     }
     else if (a == "--nee") nee = true;
+    else if (a == "--mis") mis = true;
     else if (a == "--devices") {
       const std::string v = next();
       for (size_t p = 0; p < v.size();) {
@@ -145,6 +150,10 @@ int main(int argc, char** argv) {
       std::cerr << "unknown option " << a << "\n";
       return 2;
     }
+  }
+  if (nee && mis) {
+    std::cerr << "--nee and --mis exclude each other\n";
+    return 2;
   }
   try {
     if (!std::ifstream(cameras)) {
@@ -246,7 +255,7 @@ int main(int argc, char** argv) {
       std::cout.write(bytes.data(), (std::streamsize)len);
       if (direct) std::clog << "direct: " << direct_samples << " samples, " << n_emitters << " emitters\n";
       else std::clog << "irradiance: " << irr_samples << " samples, depth " << rp.max_depth << "\n";
-    } else if (nee) {
+    } else if (nee || mis) {
       integrator::GpuRayIntegrator integ(world.get(), devices.empty() ? 0 : devices[0],
                                          precision == "fast" ? RTX_PREC_FAST : RTX_PREC_PARITY);
       const rtx_camera& dc = cam.device();
@@ -256,8 +265,8 @@ int main(int argc, char** argv) {
       rp.spp = ns, rp.max_depth = md, rp.seed = seed, rp.precision = integ.precision();
       std::vector<double> rgb(3 * npix);
       std::vector<uint32_t> segs(npix);
-      if (rtx_render_nee(integ.device_scene(), &dc, &rp, rgb.data(), segs.data()) != RTX_OK)
-        throw std::runtime_error(std::string("rtx_render_nee: ") + rtx_last_error());
+      if ((mis ? rtx_render_mis : rtx_render_nee)(integ.device_scene(), &dc, &rp, rgb.data(), segs.data()) != RTX_OK)
+        throw std::runtime_error(std::string(mis ? "rtx_render_mis: " : "rtx_render_nee: ") + rtx_last_error());
       int64_t n_emitters = 0;
       if (rtx_scene_emitters(integ.device_scene(), &n_emitters, nullptr) != RTX_OK)
         throw std::runtime_error(std::string("rtx_scene_emitters: ") + rtx_last_error());
@@ -268,7 +277,7 @@ int main(int argc, char** argv) {
       std::cout.write(bytes.data(), (std::streamsize)len);
       uint64_t total = 0;
       for (uint32_t v : segs) total += v;
-      std::clog << "nee: " << ns << " spp, " << n_emitters << " emitters, " << total << " segments\n";
+      std::clog << (mis ? "mis: " : "nee: ") << ns << " spp, " << n_emitters << " emitters, " << total << " segments\n";
     } else if (mode == "megakernel") {
       integrator::DefaultSampler fixed_sampler(ns);
       integrator::AdaptiveSampler adaptive_sampler(mk_min, ns, mk_thr);

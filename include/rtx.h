@@ -647,6 +647,36 @@ int rtx_render_nee(rtx_scene* scene, const rtx_camera* cam, const rtx_render_par
 int rtx_render_nee_device(rtx_scene* scene, const rtx_camera* cam, const rtx_render_params* params,
                           double* d_out_rgb, uint32_t* d_out_segments, void* stream);
 
+/* ---- multiple importance sampling (DESIGN.md "Multiple importance sampling") -------------------
+ * The light-sampling estimator above is noisy where a surface comes close to a light (its sample
+ * value C = g Le, g = cos_x cos_y A / (pi |y - x|^2), is unbounded), exactly where the plain
+ * estimator is good.  These entry points combine the two with the power heuristic: a third, opt-in
+ * estimator of the same radiance.  The path of (seed, pixel, sample), the emitter sample at each
+ * eligible vertex (same rule, same stream 0xA3000000 + d) and both segment counts are
+ * rtx_radiance_nee's; two weights differ.
+ *   light side: the term is (w * (C V)) * wl, wl = 1 / (1 + g^2), g the scalar of that sample: the
+ *     ratio of the BSDF's solid-angle density cos_x / pi to the light sampler's |y - x|^2 /
+ *     (A cos_y).  The term is at most w Le / 2.
+ *   BSDF side: a path that ends on an emitter (a hit below the depth limit) right after a vertex
+ *     where a term was eligible contributes wb * (throughput * Le) instead of 0, with
+ *     wb = 1 - 1 / (1 + gb^2) and gb the same ratio for the parent vertex and the hit point; a hit
+ *     primitive that is not in the emitter table (a light made by rtx_scene_update_prims: the light
+ *     sampler cannot choose it) has wb = 1, so such scenes are estimated without bias.
+ * The two weights sum to 1 at every pair of points, so the expectation is rtx_radiance's.  Emission
+ * at segment 0 and after a metal or dielectric vertex is collected unweighted, as before.  Without
+ * emitters, or with max_depth <= 1, every output equals rtx_radiance's bit for bit.
+ * Arguments, checks, their order, the max_depth cap and the outputs are those of the four entry
+ * points above; the messages say "mis" where those say "nee". */
+int rtx_radiance_mis(rtx_scene* scene, const rtx_ray* rays, const uint32_t* ids, size_t n,
+                     const rtx_radiance_params* params, double* out_rgb, uint32_t* out_segments);
+int rtx_radiance_mis_device(rtx_scene* scene, const rtx_ray* d_rays, const uint32_t* d_ids, size_t n,
+                            const rtx_radiance_params* params, double* d_out_rgb, uint32_t* d_out_segments,
+                            void* stream);
+int rtx_render_mis(rtx_scene* scene, const rtx_camera* cam, const rtx_render_params* params, double* out_rgb,
+                   uint32_t* out_segments);
+int rtx_render_mis_device(rtx_scene* scene, const rtx_camera* cam, const rtx_render_params* params,
+                          double* d_out_rgb, uint32_t* d_out_segments, void* stream);
+
 enum { RTX_DENOISE_DEMODULATE = 1 }; /* filter colour / max(albedo, 1e-3), multiply back at the end */
 typedef struct {
   int32_t iterations; /* 0..8; iteration k filters 5 x 5 taps at step 2^k; 0 copies the input */

@@ -115,6 +115,31 @@ class GpuRayIntegrator : public RayIntegrator {
     for (size_t i = 0; i < rays.size(); i++) out[i] = core::Vec3(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]);
   }
 
+  // Radiance query with multiple importance sampling: RadianceNeeBatch's arguments, paths, emitter
+  // samples and segment counts, with the power heuristic's weights on both strategies
+  // (rtx_radiance_mis): each emitter sample counts 1 / (1 + g^2) of its value, and an emitter hit
+  // right after a diffuse vertex the complementary share instead of nothing (all of it for a light
+  // the emitter table does not hold).  The same expectation, without RadianceNeeBatch's fireflies
+  // where a surface comes close to a light.  Not virtual: the reference's interface has no such call.
+  void RadianceMisBatch(const std::vector<core::Ray>& rays, std::vector<core::Vec3>& out, int spp, int max_depth,
+                        uint64_t seed, const std::vector<uint32_t>* ids = nullptr, int first_sample = 0,
+                        std::vector<uint32_t>* segments = nullptr) const {
+    out.resize(rays.size());
+    if (segments) segments->resize(rays.size());
+    if (rays.empty()) return;
+    if (ids && ids->size() != rays.size()) throw std::invalid_argument("RadianceMisBatch: one id per ray");
+    std::vector<rtx_ray> r(rays.size());
+    for (size_t i = 0; i < rays.size(); i++)
+      for (int k = 0; k < 3; k++) r[i].origin[k] = rays[i].origin()[k], r[i].direction[k] = rays[i].direction()[k];
+    rtx_radiance_params p{};
+    p.spp = spp, p.max_depth = max_depth, p.first_sample = first_sample, p.precision = precision_, p.seed = seed;
+    std::vector<double> rgb(3 * rays.size());
+    if (rtx_radiance_mis(dev_, r.data(), ids ? ids->data() : nullptr, r.size(), &p, rgb.data(),
+                         segments ? segments->data() : nullptr) != RTX_OK)
+      throw std::runtime_error(std::string("rtx_radiance_mis: ") + rtx_last_error());
+    for (size_t i = 0; i < rays.size(); i++) out[i] = core::Vec3(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]);
+  }
+
   // Irradiance query: out[i] = the cosine-weighted mean radiance arriving at points[i] over the
   // hemisphere about normals[i] (any positive finite length), from `samples` paths per point
   // traced and shaded as RadianceBatch does (rtx_irradiance: directions keyed by (seed,
