@@ -1910,7 +1910,11 @@ int film_live(const rtx_film* f) {
   if (f->sc->epoch != f->epoch) return fail(RTX_ERR_INVALID, "scene changed since the film was created");
   return RTX_OK;
 }
-int film_sampler(const rtx_film* f) { return f->prm.mode == RTX_MODE_MEGAKERNEL ? 1 : 0; }
+// the blob's sampler field: 0 wavefront family, 1 megakernel, 2 / 3 a sampled film's NEE / MIS
+int film_sampler(const rtx_film* f) {
+  if (f->estimator) return f->estimator == RTX_ESTIMATOR_MIS ? 3 : 2;
+  return f->prm.mode == RTX_MODE_MEGAKERNEL ? 1 : 0;
+}
 FilmHeader film_header(const rtx_film* f) {
   FilmHeader h{};
   std::memcpy(h.magic, kFilmMagic, sizeof h.magic);
@@ -1939,18 +1943,11 @@ int film_resolve_on(const rtx_film* f, double* d_rgb, int32_t* d_spp, hipStream_
   HIPC(hipGetLastError());
   return RTX_OK;
 }
-}  // namespace
-
-int rtx_film_create(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, rtx_film** out) {
-  if (!sc || !cam || !prm || !out) return fail(RTX_ERR_INVALID, "NULL argument");
-  *out = nullptr;
-  if (prm->max_depth < 0) return fail(RTX_ERR_INVALID, "negative max_depth");
-  if (prm->mode < RTX_MODE_WAVEFRONT || prm->mode > RTX_MODE_MEGAKERNEL) return fail(RTX_ERR_INVALID, "bad mode");
-  // AdaptiveSampler's budget is spp + 1 samples of every unfinished pixel, decided inside one
-  // call: a prefix of it is not a smaller render
-  if (prm->adaptive && prm->mode == RTX_MODE_MEGAKERNEL)
-    return fail(RTX_ERR_INVALID, "megakernel films are fixed-spp only (AdaptiveSampler does not compose across calls)");
+// The film of checked parameters: the pixel subset, the zeroed state, the scene's record of it.
+// estimator: 0, or a sampled film's (rtx_film_create_sampled).
+int film_make(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, int32_t estimator, rtx_film** out) {
   auto f = std::make_unique<rtx_film>();
+  f->estimator = estimator;
   std::string err;
   f->npix = subset_pixels(cam, prm, f->map, err);
   if (f->npix < 0) return fail(RTX_ERR_INVALID, err);
@@ -1985,6 +1982,36 @@ int rtx_film_create(rtx_scene* sc, const rtx_camera* cam, const rtx_render_param
   *out = f.release();
   return RTX_OK;
 }
+}  // namespace
+
+int rtx_film_create(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, rtx_film** out) {
+  if (!sc || !cam || !prm || !out) return fail(RTX_ERR_INVALID, "NULL argument");
+  *out = nullptr;
+  if (prm->max_depth < 0) return fail(RTX_ERR_INVALID, "negative max_depth");
+  if (prm->mode < RTX_MODE_WAVEFRONT || prm->mode > RTX_MODE_MEGAKERNEL) return fail(RTX_ERR_INVALID, "bad mode");
+  // AdaptiveSampler's budget is spp + 1 samples of every unfinished pixel, decided inside one
+  // call: a prefix of it is not a smaller render
+  if (prm->adaptive && prm->mode == RTX_MODE_MEGAKERNEL)
+    return fail(RTX_ERR_INVALID, "megakernel films are fixed-spp only (AdaptiveSampler does not compose across calls)");
+  return film_make(sc, cam, prm, 0, out);
+}
+
+int rtx_film_create_sampled(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, int32_t estimator,
+                            rtx_film** out) {
+  if (!sc || !cam || !prm || !out) return fail(RTX_ERR_INVALID, "NULL argument");
+  *out = nullptr;
+  if (estimator != RTX_ESTIMATOR_NEE && estimator != RTX_ESTIMATOR_MIS) return fail(RTX_ERR_INVALID, "bad estimator");
+  if (prm->max_depth < 0) return fail(RTX_ERR_INVALID, "negative max_depth");
+  int rc;
+  if ((rc = nee_depth_check(prm->max_depth, estimator == RTX_ESTIMATOR_MIS))) return rc;
+  if (prm->precision != RTX_PREC_PARITY && prm->precision != RTX_PREC_FAST)
+    return fail(RTX_ERR_INVALID, "sampled film: bad precision");
+  // spp, mode, flags and samples_per_group are not read: the film keeps the values a plain
+  // wavefront film has, so the two describe themselves alike
+  rtx_render_params q = *prm;
+  q.mode = RTX_MODE_WAVEFRONT, q.flags = 0, q.samples_per_group = 0;
+  return film_make(sc, cam, &q, estimator, out);
+}
 
 int rtx_film_destroy(rtx_film* f) {
   if (!f) return RTX_OK;
@@ -2013,6 +2040,7 @@ int rtx_film_reset(rtx_film* f) {
   for (DevBuf* b : {&f->sum, &f->mean, &f->m2, &f->samples, &f->conv})
     if (b->p) HIPC(hipMemsetAsync(b->p, 0, b->n, f->sc->stream));
   f->done = 0;
+  f->active = -1;
   f->aov_ready = false;
   f->epoch = f->sc->epoch;
   return RTX_OK;
@@ -2024,6 +2052,11 @@ int rtx_film_render(rtx_film* f, int32_t budget, rtx_stats* stats) {
   if (budget < 0) return fail(RTX_ERR_INVALID, "negative budget");
   if (stats) *stats = rtx_stats{};
   if (budget <= f->done) return RTX_OK;
+  if (f->estimator) {  // a sampled film: its own groups (rtx_film_sampled.h)
+    if ((rc = film_sampled_render(f, budget, stats))) return rc;
+    f->done = budget;
+    return RTX_OK;
+  }
   rtx_render_params q = f->prm;
   q.spp = budget;
   const FilmRun run{f->px(), f->done};
@@ -2137,6 +2170,7 @@ int rtx_film_load(rtx_film* f, const void* blob, size_t len) {
   if ((rc = film_pack(f, 0, s))) return rc;
   HIPC(hipStreamSynchronize(s));  // the blob is the caller's memory
   f->done = b.done;
+  f->active = -1;
   return RTX_OK;
 }
 

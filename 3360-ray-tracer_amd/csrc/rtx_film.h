@@ -36,7 +36,8 @@ struct FilmHeader {
   int32_t max_depth;      //  64
   int32_t adaptive;       //  68  0 / 1
   int32_t min_spp;        //  72
-  int32_t sampler;        //  76  0 wavefront family (wavefront, persistent), 1 megakernel
+  int32_t sampler;        //  76  0 wavefront family (wavefront, persistent), 1 megakernel,
+                          //      2 / 3 a sampled film: next-event estimation / MIS (rtx_film_create_sampled)
   double rel_threshold;   //  80
   int32_t done;           //  88  samples done (the film's budget so far)
   int32_t reserved;       //  92  0
@@ -81,7 +82,7 @@ inline std::string film_blob_error(const void* blob, size_t len, FilmHeader* out
   if (npix < 0) return "bad " + field;
   if (npix != h.npix) return "pixel count does not match the pixel map";
   if (h.adaptive != 0 && h.adaptive != 1) return "bad adaptive flag";
-  if (h.sampler != 0 && h.sampler != 1) return "bad sampler";
+  if (h.sampler < 0 || h.sampler > 3) return "bad sampler";
   if (h.sampler == 1 && h.adaptive) return "megakernel films are not adaptive";
   if (h.max_depth < 0) return "negative max_depth";
   if (h.done < 0) return "negative samples done";

@@ -107,6 +107,11 @@ struct rtx_film {
   PixelMap map{};
   int64_t npix = 0;
   int32_t done = 0;         // samples done: the film equals a one-shot render at spp = done
+  // 0: a plain film (rtx_film_create); RTX_ESTIMATOR_NEE / RTX_ESTIMATOR_MIS: a sampled film
+  // (rtx_film_create_sampled, rtx_film_sampled.h); active 0: its last render found every pixel
+  // converged, so further renders have nothing to launch (-1: not known)
+  int32_t estimator = 0;
+  int64_t active = -1;
   int64_t epoch = 0;        // the scene's epoch the film was created or last reset at (rtx_film_reset)
   DevBuf sum, mean, m2, samples, conv;  // mean / m2: adaptive films only
   mutable DevBuf stage;     // save / load: the blob's body on the device
@@ -177,6 +182,10 @@ struct rtx_scene {
   hipStream_t copy_stream = nullptr;
   std::vector<hipEvent_t> band_ev;
   AdaptWs aw;  // adaptive phases' workspace
+  // sampled films (rtx_film_sampled.h): the spread segment counters, their totals and the active
+  // lists' counts; the pinned copy of the totals and of the next list's count
+  DevBuf fs_ctr;
+  HostBuf fs_host;
   double slot_mem = -1.0;  // bytes the slot buffers may take (slot_target; -1: not yet queried)
   ~rtx_scene() {
     (void)hipSetDevice(device);
@@ -185,6 +194,7 @@ struct rtx_scene {
     // on them but rtx_film_destroy fails from now on
     for (rtx_film* f : films) f->release(), f->sc = nullptr;
     aw.release();
+    fs_ctr.release(), fs_host.release();
     for (auto e : evpool) (void)hipEventDestroy(e);
     for (auto e : band_ev) (void)hipEventDestroy(e);
     if (copy_stream) (void)hipStreamDestroy(copy_stream);
@@ -282,6 +292,16 @@ int launch_1d(K kernel, int64_t items, size_t lds, hipStream_t s, const Args&...
 int aov_on(rtx_scene* sc, const rtx_camera* cam, const PixelMap& map, int64_t npix, int32_t precision, double* d_albedo,
            double* d_normal, double* d_depth, hipStream_t s);
 int emitters_rebuild(rtx_scene* sc, hipStream_t s);
+// rtx_queries.hip: a sampled film (f->estimator != 0, alive, budget > f->done) advanced to `budget`
+// on its scene's stream (rtx_film_sampled.h); the caller sets f->done
+int film_sampled_render(rtx_film* f, int32_t budget, rtx_stats* stats);
+// next-event estimation: the vertex of segment d draws from stream kRngStreamNee + d, d < max_depth
+inline int nee_depth_check(int32_t max_depth, bool mis = false) {
+  if (max_depth > 0x00FFFFFF)
+    return fail(RTX_ERR_INVALID, mis ? "mis: max_depth above 16777215 (0x00FFFFFF)"
+                                     : "nee: max_depth above 16777215 (0x00FFFFFF)");
+  return RTX_OK;
+}
 // A call's slot scratch of the radiance queries: at most kRadianceSlots slots (448 MB), which
 // rtx_internal_radiance_chunk may raise to kRadianceSlotsMax (the test hooks' limit per call too)
 constexpr int64_t kRadianceSlots = (int64_t)1 << 24;

@@ -3,7 +3,8 @@
 // (rtx_aov*), radiance, irradiance and direct lighting on caller-supplied rays and surfels
 // (rtx_radiance*, rtx_irradiance*, rtx_direct*, rtx_scene_emitters), the light-sampling estimator
 // on rays and on the camera's own frame (rtx_radiance_nee*, rtx_render_nee*) and its power-heuristic
-// form (rtx_radiance_mis*, rtx_render_mis*), with their test hooks.
+// form (rtx_radiance_mis*, rtx_render_mis*), with their test hooks, and the render of a sampled film
+// (film_sampled_render: the frames of those two estimators kept as a film, rtx_film_sampled.h).
 // Scenes, films and the frame renderer are rtx_capi.hip's; the two share rtx_host.h.  Every query
 // picks its walk with with_walk (fast only with a fast tree, the scene's stack size).
 #include <atomic>
@@ -15,6 +16,8 @@
 #include "rtx_irradiance.h"
 #include "rtx_direct.h"
 #include "rtx_nee.h"
+#include "rtx_film_sampled.h"
+#include "rtx_scan.h"
 #include "rtx_shade_steps.h"
 #define RTX_DENOISE_AOV_KERNELS  // this translation unit holds k_aov (it needs the trace kernels)
 #include "rtx_denoise.h"
@@ -89,13 +92,6 @@ int radiance_check(const rtx_scene* sc, const rtx_radiance_params* prm, const vo
   if (prm->max_depth < 0) return fail(RTX_ERR_INVALID, "negative max_depth");
   if (prm->precision != RTX_PREC_PARITY && prm->precision != RTX_PREC_FAST)
     return fail(RTX_ERR_INVALID, "radiance: bad precision");
-  return RTX_OK;
-}
-// next-event estimation: the vertex of segment d draws from stream kRngStreamNee + d, d < max_depth
-int nee_depth_check(int32_t max_depth, bool mis = false) {
-  if (max_depth > 0x00FFFFFF)
-    return fail(RTX_ERR_INVALID, mis ? "mis: max_depth above 16777215 (0x00FFFFFF)"
-                                     : "nee: max_depth above 16777215 (0x00FFFFFF)");
   return RTX_OK;
 }
 // n > 0 rays on device buffers, in chunks of at most `cap` slots (ray x sample): whole rays per
@@ -349,7 +345,163 @@ int path_trace_hook(rtx_scene* sc, const rtx_ray* rays, const uint32_t* ids, siz
   HIPC(hipStreamSynchronize(s));
   return RTX_OK;
 }
+// ---- sampled films (rtx_film_sampled.h) ----
+// the group sizes of the calls that follow (rtx_internal_film_group; 0: the defaults)
+std::atomic<int32_t> g_film_group_first{0}, g_film_group_later{0};
+// Samples per entry of an adaptive film's groups after the first: the reference tests after every
+// sample, so at most kFilmGroup - 1 traced samples of a pixel are discarded.
+constexpr int32_t kFilmGroup = 4;
 }  // namespace
+
+// A sampled film advanced to `budget`.  Fixed: samples [done, budget) of every pixel, in chunks
+// under the slot cap (whole pixels per chunk, or one pixel's samples in runs), each traced and
+// added in sample order.  Adaptive: every pixel still sampling holds the same count, so a group is
+// G samples of every entry of the active list; an empty film starts with min(min_spp, budget)
+// samples of every pixel (nothing can converge earlier), a film that holds samples with a pass of
+// no samples that lists its unconverged pixels.  After each group the next list's count comes back
+// through a pinned word (the next launch is sized by it), and the call ends when it is 0 or the
+// budget is reached.
+int film_sampled_render(rtx_film* f, int32_t budget, rtx_stats* stats) {
+  rtx_scene* sc = f->sc;
+  const int64_t npix = f->npix;
+  const bool adaptive = f->prm.adaptive != 0;
+  if (npix == 0 || (adaptive && f->active == 0)) return RTX_OK;
+  HIPC(hipSetDevice(sc->device));
+  hipStream_t s = sc->stream;
+  const bool mis = f->estimator == RTX_ESTIMATOR_MIS;
+  const int64_t tuned = g_radiance_chunk.load();
+  const int64_t cap = std::min<int64_t>(tuned > 0 ? tuned : kRadianceSlots, kRadianceSlotsMax);
+  int rc;
+  if ((rc = sc->fs_ctr.reserve(kFilmCtrWords * sizeof(unsigned long long)))) return rc;
+  if ((rc = sc->fs_host.reserve(4 * sizeof(unsigned long long)))) return rc;
+  unsigned long long* const ctr = sc->fs_ctr.as<unsigned long long>();
+  uint32_t* const counts = (uint32_t*)(ctr + kFilmCtrTotals + 2);  // the two lists' counts
+  volatile unsigned long long* const pin = (volatile unsigned long long*)sc->fs_host.p;
+  HIPC(hipMemsetAsync(ctr, 0, kFilmCtrWords * sizeof(unsigned long long), s));
+  AdaptWs& w = sc->aw;
+  if (adaptive) {
+    for (DevBuf* b : {&w.lst[0], &w.lst[1], &w.knext})
+      if ((rc = b->reserve((size_t)npix * sizeof(uint32_t)))) return rc;
+    if ((rc = w.pk.reserve((size_t)npix * sizeof(uint64_t)))) return rc;
+    if ((rc = w.scan_tmp.reserve(rtxscan::temp_bytes_packed(npix)))) return rc;
+  }
+  const NeeCamera nc{f->cam, f->map};
+  const EmitterTable E = emitter_table(sc);
+  const PixelSoA px = f->px();
+  // timing: the call between ev[0] and ev[1], each path launch between a pair of the pool
+  const bool timed = stats != nullptr;
+  size_t evi = 0;
+  auto ev_at = [&](size_t i) -> hipEvent_t {
+    while (sc->evpool.size() <= i) {
+      hipEvent_t e = nullptr;
+      if (hipEventCreate(&e) != hipSuccess) return nullptr;
+      sc->evpool.push_back(e);
+    }
+    return sc->evpool[i];
+  };
+  uint64_t slots_traced = 0, hot_launches = 0;
+  if (timed) HIPC(hipEventRecord(sc->ev[0], s));
+  FilmGroup A{};
+  A.max_depth = f->prm.max_depth, A.seed = f->prm.seed, A.npix = (uint32_t)npix;
+  FilmRecord R{};
+  R.min_spp = f->prm.min_spp, R.budget = budget, R.rel = f->prm.rel_threshold;
+  R.keep = adaptive ? w.knext.as<uint32_t>() : nullptr, R.ctr = ctr;
+  // entries [A.e0, A.e0 + A.ne) of the group in A: traced into the slot scratch, then recorded
+  auto launch = [&]() -> int {
+    const int64_t slots = (int64_t)A.ne * A.G;
+    if (slots > 0) {
+      int r;
+      if ((r = sc->rad_L.reserve((size_t)slots * 3 * sizeof(double)))) return r;
+      if ((r = sc->rad_segs.reserve((size_t)slots * sizeof(uint32_t)))) return r;
+      A.L = sc->rad_L.as<double>(), A.segs = sc->rad_segs.as<uint32_t>();
+      hipEvent_t e0 = nullptr, e1 = nullptr;
+      if (timed) {
+        e0 = ev_at(evi), e1 = ev_at(evi + 1);
+        if (!e0 || !e1) return fail(RTX_ERR_HIP, "hipEventCreate failed");
+        evi += 2;
+        HIPC(hipEventRecord(e0, s));
+      }
+      if ((r = with_walk(sc, f->prm.precision, [&](auto wk) {
+             constexpr size_t lds = stack_lds_bytes(wk.stack);
+             if (mis) return launch_1d(k_film_paths<wk.stack, wk.fast, true>, slots, lds, s, sc->S, E, nc, A);
+             return launch_1d(k_film_paths<wk.stack, wk.fast, false>, slots, lds, s, sc->S, E, nc, A);
+           })))
+        return r;
+      if (timed) HIPC(hipEventRecord(e1, s));
+      slots_traced += (uint64_t)slots, hot_launches++;
+    }
+    if (adaptive) return launch_1d(k_film_record<true>, A.ne, 0, s, px, A, R);
+    return launch_1d(k_film_record<false>, A.ne, 0, s, px, A, R);
+  };
+  if (!adaptive) {
+    const int64_t todo = (int64_t)budget - f->done;
+    const int64_t k_per = std::min<int64_t>(todo, cap), pix_per = std::max<int64_t>(1, cap / todo);
+    A.list = nullptr, A.count = nullptr, A.bound = (uint32_t)npix;
+    for (int64_t r0 = 0; r0 < npix; r0 += pix_per)
+      for (int64_t k0 = 0; k0 < todo; k0 += k_per) {
+        A.e0 = (uint32_t)r0, A.ne = (uint32_t)std::min<int64_t>(pix_per, npix - r0);
+        A.G = (uint32_t)std::min<int64_t>(k_per, todo - k0), A.s0 = (int32_t)(f->done + k0);
+        if ((rc = launch())) return rc;
+      }
+  } else {
+    const int32_t g_first = g_film_group_first.load(), g_later = g_film_group_later.load();
+    int cur = -1;                 // the list in use: w.lst[cur], or none yet (every pixel)
+    int64_t n_active = npix;      // its entries, as the host knows them
+    int32_t have = f->done;       // samples every entry of the list holds
+    bool first = f->done == 0;
+    // the group in A recorded over all its entries; then the next list and its count
+    auto group = [&](int32_t G) -> int {
+      const int64_t per = G > 0 ? std::max<int64_t>(1, cap / G) : n_active;
+      A.list = cur < 0 ? nullptr : w.lst[cur].as<uint32_t>(), A.count = cur < 0 ? nullptr : counts + cur;
+      A.bound = (uint32_t)n_active, A.G = (uint32_t)G, A.s0 = have;
+      for (int64_t e0 = 0; e0 < n_active; e0 += per) {
+        A.e0 = (uint32_t)e0, A.ne = (uint32_t)std::min<int64_t>(per, n_active - e0);
+        int r;
+        if ((r = launch())) return r;
+      }
+      const int nxt = cur == 0 ? 1 : 0;
+      HIPC(rtxscan::exclusive_scan_packed(R.keep, w.pk.as<uint64_t>(), n_active, w.scan_tmp.p, w.scan_tmp.n, s));
+      int r;
+      if ((r = launch_1d(k_film_emit, n_active, 0, s, A.list, (const uint32_t*)R.keep, (const uint64_t*)w.pk.as<uint64_t>(),
+                         (uint32_t)n_active, (uint32_t)npix, w.lst[nxt].as<uint32_t>(), counts + nxt)))
+        return r;
+      HIPC(hipMemcpyAsync((void*)(pin + 2), counts + nxt, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+      HIPC(hipStreamSynchronize(s));
+      n_active = std::min<int64_t>((int64_t)(uint32_t)pin[2], n_active);  // (a list only shrinks)
+      cur = nxt, have += G;
+      return RTX_OK;
+    };
+    if (!first && (rc = group(0))) return rc;  // who is still sampling
+    while (n_active > 0 && have < budget) {
+      int32_t G = first ? (g_first > 0 ? g_first : std::max(1, f->prm.min_spp)) : (g_later > 0 ? g_later : kFilmGroup);
+      G = (int32_t)std::min<int64_t>(std::min<int64_t>(G, budget - have), cap);
+      if ((rc = group(G))) return rc;
+      first = false;
+    }
+    // an empty list below the budget: every pixel has converged (at the budget the list is empty
+    // either way, and who has converged is not known here)
+    f->active = have < budget ? n_active : -1;
+  }
+  if (timed) {
+    HIPC(hipEventRecord(sc->ev[1], s));
+    hipLaunchKernelGGL(k_film_totals, dim3(1), dim3(64), 0, s, ctr);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync((void*)pin, ctr + kFilmCtrTotals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    float ms = 0;
+    HIPC(hipEventElapsedTime(&ms, sc->ev[0], sc->ev[1]));
+    double hot_ms = 0;
+    for (size_t e = 0; e + 1 < evi; e += 2) {
+      float hms = 0;
+      HIPC(hipEventElapsedTime(&hms, sc->evpool[e], sc->evpool[e + 1]));
+      hot_ms += hms;
+    }
+    stats->paths = stats->rays_primary = slots_traced;
+    stats->rays_total = pin[0], stats->rays_recorded = pin[1];
+    stats->kernel_ms = ms, stats->hot_kernel_ms = hot_ms, stats->hot_launches = hot_launches;
+  }
+  return RTX_OK;
+}
 
 extern "C" {
 
@@ -722,6 +874,15 @@ int rtx_internal_shade_steps(rtx_scene* sc, const void* cases, size_t n, int32_t
 int rtx_internal_radiance_chunk(int64_t slots) {
   if (slots < 0) return fail(RTX_ERR_INVALID, "radiance chunk: negative slot count");
   g_radiance_chunk.store(slots);
+  return RTX_OK;
+}
+
+// Test hook (not in rtx.h): the samples per entry of an adaptive sampled film's first group (on
+// an empty film) and of its later groups, for the rtx_film_render calls that follow in this
+// process (0 restores min_spp and kFilmGroup).  Results never depend on them.
+int rtx_internal_film_group(int32_t first, int32_t later) {
+  if (first < 0 || later < 0) return fail(RTX_ERR_INVALID, "film group: negative group size");
+  g_film_group_first.store(first), g_film_group_later.store(later);
   return RTX_OK;
 }
 

@@ -54,6 +54,11 @@ class WavefrontRenderer {
   // parameters (rtx_film_denoise_p3: one device renders through a film; several devices: the
   // gathered frame through rtx_aov + rtx_denoise).  framebuffer() stays the unfiltered frame.
   void set_denoise(bool on) { denoise_ = on; }
+  // Render() through a sampled film (rtx_film_create_sampled): the frame of the light-sampling
+  // estimator (RTX_ESTIMATOR_NEE) or of its power-heuristic form (RTX_ESTIMATOR_MIS), fixed spp or
+  // (set_adaptive) with per-pixel adaptive sampling; set_progressive, set_checkpoint, set_resume,
+  // set_preview and set_denoise apply to it.  0: the plain renderer.  One device; set_mode is not read.
+  void set_estimator(int estimator) { estimator_ = estimator; }
   void set_seed(uint64_t s) { params_.seed = s; }
   void set_adaptive(bool on) { params_.adaptive = on ? 1 : 0; }
   void set_mode(int mode) { params_.mode = mode; }
@@ -76,6 +81,7 @@ class WavefrontRenderer {
   int stripe_rows_ = 8;
   int chunks_ = 0;                    // > 0: progressive (set_progressive)
   bool denoise_ = false;              // set_denoise
+  int estimator_ = 0;                 // set_estimator
   std::string checkpoint_, resume_;
   std::function<void(int, const std::string&)> preview_;
   void RenderFilm(integrator::GpuRayIntegrator* gpu, const rtx_render_params& p, std::ostream& out);

@@ -181,11 +181,11 @@ void WavefrontRenderer::Render(std::ostream& out) {
   rgb_.assign(3 * n, 0.0);
   spp_.assign(n, 0);
   // wavefront.cc:238-241: the P3 text is formatted on the device (rtx_render_p3)
-  if (chunks_ > 0 || !checkpoint_.empty() || !resume_.empty()) {
+  if (chunks_ > 0 || !checkpoint_.empty() || !resume_.empty() || estimator_ != 0) {
     if (devices_.size() > 1)
       throw std::invalid_argument(
-          "WavefrontRenderer: set_progressive / set_checkpoint / set_resume render through one film on one device; "
-          "not with set_devices / set_gpus");
+          "WavefrontRenderer: set_progressive / set_checkpoint / set_resume / set_estimator render through one film "
+          "on one device; not with set_devices / set_gpus");
     RenderFilm(gpu, p, out);
     return;
   }
@@ -241,7 +241,10 @@ void WavefrontRenderer::RenderFilm(integrator::GpuRayIntegrator* gpu, const rtx_
     rtx_film* f = nullptr;
     ~Owner() { rtx_film_destroy(f); }
   } film;
-  if (rtx_film_create(gpu->device_scene(), &dc, &p, &film.f) != RTX_OK)
+  if (estimator_ != 0) {
+    if (rtx_film_create_sampled(gpu->device_scene(), &dc, &p, estimator_, &film.f) != RTX_OK)
+      throw std::runtime_error(std::string("rtx_film_create_sampled: ") + rtx_last_error());
+  } else if (rtx_film_create(gpu->device_scene(), &dc, &p, &film.f) != RTX_OK)
     throw std::runtime_error(std::string("rtx_film_create: ") + rtx_last_error());
   if (!resume_.empty()) {
     std::ifstream in(resume_, std::ios::binary);
@@ -266,6 +269,7 @@ void WavefrontRenderer::RenderFilm(integrator::GpuRayIntegrator* gpu, const rtx_
       throw std::runtime_error(std::string("rtx_film_render: ") + rtx_last_error());
     stats_.rays_primary += st.rays_primary, stats_.rays_total += st.rays_total, stats_.paths += st.paths;
     stats_.kernel_ms += st.kernel_ms, stats_.hot_kernel_ms += st.hot_kernel_ms, stats_.hot_launches += st.hot_launches;
+    stats_.rays_recorded += st.rays_recorded;
     if (st.hot_launches) stats_.build = st.build, stats_.parked = st.parked, stats_.node_bytes = st.node_bytes;
     if (preview_ && k < chunks) {
       p3();

@@ -147,7 +147,8 @@ EXPORTS = ["rtx_abi_version", "rtx_last_error", "rtx_device_count", "rtx_scene_c
            "rtx_occluded", "rtx_occluded_device", "rtx_ao", "rtx_ao_device", "rtx_radiance", "rtx_radiance_device",
            "rtx_irradiance", "rtx_irradiance_device", "rtx_direct", "rtx_direct_device", "rtx_scene_emitters",
            "rtx_radiance_nee", "rtx_radiance_nee_device", "rtx_render_nee", "rtx_render_nee_device",
-           "rtx_radiance_mis", "rtx_radiance_mis_device", "rtx_render_mis", "rtx_render_mis_device"]
+           "rtx_radiance_mis", "rtx_radiance_mis_device", "rtx_render_mis", "rtx_render_mis_device",
+           "rtx_film_create_sampled"]
 
 _lib = None
 
@@ -193,6 +194,7 @@ def lib():
             "rtx_encode_p3": ([vp, vp, i32, i32, vp, sz, C.POINTER(sz)], C.c_int),
             "rtx_image_load": ([C.c_char_p, i32, C.POINTER(i32), C.POINTER(i32), vp, sz], C.c_int),
             "rtx_film_create": ([vp, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(vp)], C.c_int),
+            "rtx_film_create_sampled": ([vp, C.POINTER(Camera), C.POINTER(RenderParams), i32, C.POINTER(vp)], C.c_int),
             "rtx_film_destroy": ([vp], C.c_int),
             "rtx_film_render": ([vp, i32, C.POINTER(Stats)], C.c_int),
             "rtx_film_samples": ([vp, C.POINTER(i32)], C.c_int),
@@ -376,9 +378,12 @@ class DeviceScene:
 
     def film(self, cam, max_depth, seed=1234, adaptive=True, mode="wavefront", precision="parity", tile=None,
              stripes=None, samples_per_group=0, min_spp=16, rel_threshold=float(np.float32(0.05)), schedule=None,
-             generic=False):
+             generic=False, estimator=None):
         """A resumable frame on this scene (rtx_film_create): render(budget) advances it, and after
-        each call it equals the one-shot render(...) of the same arguments at spp = budget."""
+        each call it equals the one-shot render(...) of the same arguments at spp = budget.
+        estimator "nee" / "mis": a sampled film (rtx_film_create_sampled), the frame of render_nee /
+        render_mis kept as a film, fixed spp (adaptive=False) or with per-pixel adaptive sampling;
+        mode, schedule, generic and samples_per_group are not read."""
         p = RenderParams()
         p.spp, p.max_depth, p.adaptive = 0, max_depth, int(bool(adaptive))
         p.min_spp, p.rel_threshold, p.seed = min_spp, rel_threshold, seed
@@ -389,7 +394,7 @@ class DeviceScene:
             p.stripe_rows, p.stripe_index, p.stripe_count = stripes
         elif tile is not None:
             p.x0, p.y0, p.w, p.h = tile
-        return Film(self, cam, p)
+        return Film(self, cam, p, ESTIMATORS[estimator])
 
     def intersect(self, rays, tmin=RTX_SEAM_TMIN, tmax=float("inf"), precision="parity"):
         rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
@@ -743,11 +748,15 @@ class DeviceScene:
         return st.as_dict() if stats else None
 
 
+RTX_ESTIMATOR_NEE, RTX_ESTIMATOR_MIS = 1, 2
+ESTIMATORS = {None: 0, "nee": RTX_ESTIMATOR_NEE, "mis": RTX_ESTIMATOR_MIS}
+
+
 class Film:
     """A frame rendered in steps (rtx_film_*): the per-pixel state stays on the scene's device
     between calls.  Made by DeviceScene.film(); it keeps its scene alive."""
 
-    def __init__(self, scene, cam, params):
+    def __init__(self, scene, cam, params, estimator=0):
         self.scene = scene
         self.h = C.c_void_p()
         n = lib().rtx_render_pixel_count(C.byref(cam), C.byref(params))
@@ -755,7 +764,11 @@ class Film:
             _check(n, "rtx_render_pixel_count")
         self.npix = n
         self._p3_cap = lib().rtx_p3_max_bytes(cam.image_width, cam.image_height)
-        _check(lib().rtx_film_create(scene.h, C.byref(cam), C.byref(params), C.byref(self.h)), "rtx_film_create")
+        if estimator:
+            _check(lib().rtx_film_create_sampled(scene.h, C.byref(cam), C.byref(params), estimator, C.byref(self.h)),
+                   "rtx_film_create_sampled")
+        else:
+            _check(lib().rtx_film_create(scene.h, C.byref(cam), C.byref(params), C.byref(self.h)), "rtx_film_create")
 
     def close(self):
         if getattr(self, "h", None) and _lib is not None:
@@ -1085,6 +1098,16 @@ def radiance_chunk(slots=0):
     f.argtypes = [C.c_int64]
     f.restype = C.c_int
     _check(f(slots), "rtx_internal_radiance_chunk")
+
+
+def film_group(first=0, later=0):
+    """Test hook (rtx_internal_film_group, not in rtx.h): the samples per pixel of an adaptive sampled
+    film's first group (on an empty film) and of its later groups, for the render calls that follow
+    in this process; 0 restores the defaults (min_spp, 4).  Results never depend on them."""
+    f = lib().rtx_internal_film_group
+    f.argtypes = [C.c_int32, C.c_int32]
+    f.restype = C.c_int
+    _check(f(first, later), "rtx_internal_film_group")
 
 
 def adapt_tune(phase_slots=0, phase_kcap=0, first_map=-1, phase_mstep=-1.0, margin1=-1.0, pool_w=-1.0):

@@ -4,7 +4,7 @@
 //             [--mode wavefront|persistent|megakernel] [--precision parity|fast]
 //             [--mk-adaptive MIN:THRESHOLD] [--gpus N]
 //             [--chunks N] [--preview PREFIX] [--checkpoint FILE] [--resume FILE] [--denoise]
-//             [--ao N[,RADIUS]] [--irradiance N[,DEPTH]] [--direct N] [--nee | --mis] > out.ppm
+//             [--ao N[,RADIUS]] [--irradiance N[,DEPTH]] [--direct N] [--nee | --mis] [--adaptive] > out.ppm
 // --gpus N renders one frame over N GPUs (interleaved row stripes, one host thread per GPU,
 // one gathered framebuffer and P3 output; identical pixels for every N); --devices 0,2,3
 // names the devices (a device may repeat: several streams on one GPU).
@@ -36,6 +36,12 @@
 // --mis writes the frame of the combined estimator in the same way (rtx_render_mis: the same paths
 // and emitter samples, the two strategies weighted with the power heuristic, so a lamp close to a
 // wall leaves no fireflies); --nee and --mis together is an error.
+// --nee / --mis with any of --chunks, --preview, --checkpoint, --resume, --denoise or --adaptive render
+// the estimator's frame through a sampled film (rtx_film_create_sampled): those options then work as
+// they do for the plain render, and without --adaptive the bytes on stdout are those of the plain
+// --nee / --mis run at the same spp.  --adaptive samples every pixel until it converges (the
+// renderer's own test, 16 samples at least, threshold 0.05f) or reaches the spp.  The run logs
+// "mis film: <budget> spp, <emitters> emitters, <traced> segments traced, <recorded> recorded".
 // --mk-adaptive selects the AdaptiveSampler (sampler.h:44-82) for --mode megakernel,
 // with max_samples = the preset's (or --spp) samples.
 // Defaults follow main.cc: preset "default" (fallback when unknown), the Cornell box
@@ -61,6 +67,7 @@ int main(int argc, char** argv) {
   int spp = -1, depth = -1;
   uint64_t seed = 1234;
   bool fixed = false, denoise = false;
+  bool adaptive = false;  // --adaptive (with --nee / --mis)
   std::vector<int> devices;
   int mk_min = -1, gpus = 1, chunks = 0, ao_samples = 0;
   int irr_samples = 0, irr_depth = -1;  // --irradiance (depth -1: the preset's)
@@ -95,6 +102,7 @@ int main(int argc, char** argv) {
     else if (a == "--checkpoint") checkpoint = next();
     else if (a == "--resume") resume = next();
     else if (a == "--denoise") denoise = true;
+    else if (a == "--adaptive") adaptive = true;
     else if (a == "--ao") {
       const std::string v = next();
       const size_t c = v.find(',');
@@ -153,6 +161,10 @@ int main(int argc, char** argv) {
   }
   if (nee && mis) {
     std::cerr << "--nee and --mis exclude each other\n";
+    return 2;
+  }
+  if (adaptive && !nee && !mis) {
+    std::cerr << "--adaptive needs --nee or --mis (the plain render is adaptive unless --fixed)\n";
     return 2;
   }
   try {
@@ -255,6 +267,31 @@ int main(int argc, char** argv) {
       std::cout.write(bytes.data(), (std::streamsize)len);
       if (direct) std::clog << "direct: " << direct_samples << " samples, " << n_emitters << " emitters\n";
       else std::clog << "irradiance: " << irr_samples << " samples, depth " << rp.max_depth << "\n";
+    } else if ((nee || mis) && (film || denoise || adaptive)) {  // the estimator's frame through a sampled film
+      integrator::GpuRayIntegrator integ(world.get(), devices.empty() ? 0 : devices[0],
+                                         precision == "fast" ? RTX_PREC_FAST : RTX_PREC_PARITY);
+      renderer::WavefrontRenderer r(*world, cam, integ, md, ns, 2 * 8192);
+      r.set_seed(seed);
+      r.set_adaptive(adaptive);
+      r.set_precision(precision == "fast" ? RTX_PREC_FAST : RTX_PREC_PARITY);
+      r.set_estimator(mis ? RTX_ESTIMATOR_MIS : RTX_ESTIMATOR_NEE);
+      if (film) r.set_progressive(chunks > 0 ? chunks : 1);
+      if (!checkpoint.empty()) r.set_checkpoint(checkpoint);
+      if (!resume.empty()) r.set_resume(resume);
+      r.set_denoise(denoise);
+      if (!preview.empty())
+        r.set_preview([&](int budget, const std::string& p3) {
+          const std::string path = preview + "_" + std::to_string(budget) + ".ppm";
+          std::ofstream o(path, std::ios::binary);
+          o.write(p3.data(), (std::streamsize)p3.size());
+          if (!o) throw std::runtime_error("cannot write " + path);
+        });
+      r.Render();
+      int64_t n_emitters = 0;
+      if (rtx_scene_emitters(integ.device_scene(), &n_emitters, nullptr) != RTX_OK)
+        throw std::runtime_error(std::string("rtx_scene_emitters: ") + rtx_last_error());
+      std::clog << (mis ? "mis film: " : "nee film: ") << ns << " spp, " << n_emitters << " emitters, "
+                << r.stats().rays_total << " segments traced, " << r.stats().rays_recorded << " recorded\n";
     } else if (nee || mis) {
       integrator::GpuRayIntegrator integ(world.get(), devices.empty() ? 0 : devices[0],
                                          precision == "fast" ? RTX_PREC_FAST : RTX_PREC_PARITY);

@@ -425,6 +425,23 @@ typedef struct rtx_film rtx_film;
  * ignored.  RTX_MODE_MEGAKERNEL with adaptive is RTX_ERR_INVALID (AdaptiveSampler's spp + 1
  * budget does not compose across calls). */
 int rtx_film_create(rtx_scene* scene, const rtx_camera* cam, const rtx_render_params* params, rtx_film** out);
+/* A film of the light-sampling estimators (DESIGN.md "Sampled films"): estimator RTX_ESTIMATOR_NEE
+ * is the frame of rtx_render_nee kept as a film, RTX_ESTIMATOR_MIS that of rtx_render_mis.  Of params
+ * it reads max_depth, adaptive, min_spp, rel_threshold, seed, precision and the tile and stripe
+ * fields; spp, mode, flags and samples_per_group are ignored.  adaptive 0: after
+ * rtx_film_render(film, b) the film resolves to rtx_render_nee / rtx_render_mis at spp = b bit for
+ * bit, however the budget was split over calls.  adaptive != 0: every pixel records its samples in
+ * order with RecordSample / IsConverged (the renderer's adaptive sampling), tested after every sample
+ * from min_spp on, and stops at its first converged sample or at the budget.  Checks, in this order:
+ * NULL arguments, "bad estimator", negative max_depth, max_depth above 16777215 ("nee:" / "mis:"),
+ * bad precision, the pixel subset.  Every other rtx_film_* call works on such a film as on a plain
+ * one; its blob carries sampler 2 (NEE) or 3 (MIS) and loads only into a film of the same estimator.
+ * rtx_stats of a render: paths = rays_primary = samples traced, rays_total = closest-hit plus
+ * shadow segments traced, rays_recorded = those of the samples the pixels recorded (fixed:
+ * = rays_total), kernel_ms, hot_kernel_ms / hot_launches of the path kernel; the rest 0. */
+enum { RTX_ESTIMATOR_NEE = 1, RTX_ESTIMATOR_MIS = 2 };
+int rtx_film_create_sampled(rtx_scene* scene, const rtx_camera* cam, const rtx_render_params* params,
+                            int32_t estimator, rtx_film** out);
 int rtx_film_destroy(rtx_film* film);
 /* Advance the film to `budget` samples: fixed sampling traces samples [done, budget) of every
  * pixel; adaptive sampling continues every pixel that has not converged up to budget (the first
