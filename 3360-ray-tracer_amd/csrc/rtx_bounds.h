@@ -70,6 +70,29 @@ RTX_HD inline void ref_bounds(int32_t kind, const double* g, double* out) {
   ordered(g[4] - 0.0001, g[4] + 0.0001, out[ax], out[3 + ax]);
 }
 
+// SAH bin (of 16) of a centroid coordinate c in a node whose centroids start at mn, inv =
+// 1 / extent (bvh.h:230-236): trunc((c - mn) * inv * 16), clamped to [0, 15].  An extent below
+// 2^-1024 makes inv +inf and the product +inf (c > mn) or NaN (c == mn); converting those to
+// int is undefined in C++ and differs by machine (x86 cvttsd2si gives INT_MIN, gfx950
+// saturates +inf to INT_MAX).  The rule here is what the reference's x86 build does: a product
+// that is NaN or not below 2^31 goes to bin 0.  Every other value converts as the bare cast.
+RTX_HD inline int sah_bin(double c, double mn, double inv) {
+  const double v = (c - mn) * inv * 16;
+  if (!(v < 2147483648.0) || v < 0.0) return 0;
+  const int b = (int)v;
+  return b > 15 ? 15 : b;
+}
+
+// Index of the first of n boxes (6 doubles each) with a NaN or infinite bound, -1 if all are
+// finite.  The raw-box builders refuse such input: a NaN bound or centroid compares equal to
+// nothing, which the device build's "first position holding the extreme" search relies on.
+inline int64_t first_nonfinite_box(const double* bounds, int64_t n) {
+  for (int64_t i = 0; i < n; i++)
+    for (int c = 0; c < 6; c++)
+      if (!isfinite(bounds[6 * i + c])) return i;
+  return -1;
+}
+
 // Conservative f64 box of one primitive (fast-path leaf splitting).  Spheres: centre +-
 // |r|; rects: the rectangle on its plane; triangles: the vertex box padded by 2^-19 of its
 // largest extent, which covers the points the reference's float-rounded barycentric test

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "rtx.h"
+#include "rtx_bounds.h"
 
 extern "C" void rtx_internal_set_error(const char* msg);  // rtx_capi.hip
 
@@ -97,10 +98,8 @@ __device__ __forceinline__ double area(const double lo[3], const double hi[3]) {
   const double dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
   return 2.0 * (dx * dy + dy * dz + dz * dx);
 }
-__device__ __forceinline__ int bin_of(double c, double mn, double inv) {
-  const int b = (int)((c - mn) * inv * 16);
-  return b < 0 ? 0 : (b > 15 ? 15 : b);
-}
+// the host builder's explicit conversion rule (rtx_bounds.h): inf / NaN -> bin 0
+__device__ __forceinline__ int bin_of(double c, double mn, double inv) { return rtxb::sah_bin(c, mn, inv); }
 // Interval union with std::min/std::max: first operand wins ties
 __device__ __forceinline__ void unite(double lo[3], double hi[3], const double l2[3], const double h2[3]) {
   for (int a = 0; a < 3; a++) {
@@ -125,7 +124,12 @@ __global__ __launch_bounds__(kB) void k_build_level(Args A, int32_t level_begin)
   const double* __restrict__ B = A.bounds;
   int32_t* __restrict__ idx = A.idx;
 
-  // ---- node box (coords 0..5) and centroid box (6..11): key min/max, then first position
+  // ---- node box (coords 0..5) and centroid box (6..11): key min/max, then first position.
+  // Every position found below (pos / s_pos here, s_bpos per bin) is inside [s, e): the entry
+  // point refuses NaN and infinite bounds, and a centroid 0.5 * (lo + hi) of finite values is
+  // never NaN (at worst +-inf, which equals itself).  So each winning key decodes to a value
+  // that the primitive it came from compares equal to, and the search cannot come back empty
+  // (0xffffffff) and index idx[] out of range.
   {
     uint64_t k[12];
     for (int c = 0; c < 12; c++) k[c] = (c % 6) < 3 ? ~0ull : 0ull;
@@ -372,6 +376,8 @@ extern "C" int rtx_bvh_build(int device, const double* bounds, int64_t n, rtx_bv
   if (!bounds && n > 0) return err("rtx_bvh_build: bounds is NULL");
   if (!out_nodes || !out_n_nodes || !out_prim_indices) return err("rtx_bvh_build: NULL output");
   if (n < 0 || n > 0x3FFFFFFF) return err("rtx_bvh_build: primitive count out of range");
+  if (const int64_t bad = rtxb::first_nonfinite_box(bounds, n); bad >= 0)
+    return err("rtx_bvh_build: box " + std::to_string(bad) + " has a NaN or infinite bound");
   *out_n_nodes = 0;
   if (n == 0) return RTX_OK;
   auto hip = [&](hipError_t e, const char* what) {

@@ -119,6 +119,8 @@ int rtx_bvh_build_host(const double* bounds, int64_t n, rtx_bvh_node* out_nodes,
   if ((!bounds && n > 0) || !out_nodes || !out_n_nodes || !out_prim_indices)
     return host_fail(RTX_ERR_INVALID, "NULL argument");
   if (n < 0 || n > 0x3FFFFFFF) return host_fail(RTX_ERR_INVALID, "primitive count out of range");
+  if (const int64_t bad = rtxb::first_nonfinite_box(bounds, n); bad >= 0)
+    return host_fail(RTX_ERR_INVALID, "rtx_bvh_build_host: box " + std::to_string(bad) + " has a NaN or infinite bound");
   std::vector<rt::geom::Aabb> b(n);
   for (int64_t i = 0; i < n; i++) {
     const double* q = bounds + 6 * i;

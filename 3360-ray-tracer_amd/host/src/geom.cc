@@ -10,6 +10,7 @@
 #include "rt/geom.h"
 #include "rt/material.h"
 #include "rt/scene.h"
+#include "rtx_bounds.h"
 
 namespace rt::geom {
 
@@ -71,10 +72,8 @@ struct SahBuilder {
   std::vector<core::Vec3> centroids;
   std::vector<BvhNodeGPU>& out;
 
-  static int Bin(double c, double mn, double inv) {
-    int b = static_cast<int>((c - mn) * inv * 16);
-    return b < 0 ? 0 : (b > 15 ? 15 : b);
-  }
+  // the explicit conversion rule the device build shares (rtx_bounds.h): inf / NaN -> bin 0
+  static int Bin(double c, double mn, double inv) { return rtxb::sah_bin(c, mn, inv); }
 
   // two-ended partition (libstdc++ __partition, bidirectional_iterator_tag)
   template <class Pred>

@@ -378,10 +378,16 @@ int rtx_prim_bounds(const rtx_prim* prims, int64_t n, double* out_bounds);
 /* Binned-SAH BVH over n primitive boxes (in the primitives' original order), built on the
    GPU.  Output is byte-identical to the host builder's (= the reference's Bvh::Build):
    out_nodes (capacity 2n) in pre-order, *out_n_nodes, out_prim_indices[n] (the permutation:
-   leaf slot -> original primitive).  Host buffers; the device work is internal. */
+   leaf slot -> original primitive).  Host buffers; the device work is internal.
+   All 6n bounds must be finite: a NaN or infinite bound is refused on the host, before any
+   device call, with RTX_ERR_INVALID and a message naming the first such box (any finite value
+   is fine, e.g. lo = -1.7e308, hi = 1.7e308).  lo <= hi is not required.  SAH bins are
+   trunc((c - mn) / extent * 16) clamped to [0, 15]; where a centroid extent below 2^-1024 makes
+   that product infinite or NaN, the bin is 0 (what the reference's x86 build computes). */
 int rtx_bvh_build(int device, const double* bounds, int64_t n, rtx_bvh_node* out_nodes, int64_t* out_n_nodes,
                   uint32_t* out_prim_indices);
-/* The same build on the host (the C++ builder scene assembly uses); identical outputs. */
+/* The same build on the host (the C++ builder scene assembly uses); identical outputs, and the
+   same refusal of non-finite bounds. */
 int rtx_bvh_build_host(const double* bounds, int64_t n, rtx_bvh_node* out_nodes, int64_t* out_n_nodes,
                        uint32_t* out_prim_indices);
 

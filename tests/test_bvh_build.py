@@ -2,7 +2,10 @@
 produce the reference's node array and prim_indices byte for byte.  The host builder is
 pinned to the reference's own Bvh::Build by tests/golden (test_oracle_golden.py BVH dumps
 and hashes); here the raw-box entry points are checked against the scenes' BVHs, and the
-device build against the host build on the scenes and on adversarial box sets."""
+device build against the host build on the scenes, on adversarial box sets and on the crafted
+families of tests/bvh_build_cases.py (which tests/test_bvh_build_host.py shows to reach their
+targets and pins to the oracle on the CPU)."""
+import ctypes
 import hashlib
 import json
 import os
@@ -10,6 +13,7 @@ import os
 import numpy as np
 import pytest
 
+import bvh_build_cases as cases
 from conftest import GOLDEN, scene_path
 
 BVH_SCENES = ["cornell", "final", "bunny", "mixed"]
@@ -102,7 +106,103 @@ def test_device_build_equals_host_adversarial(rtx_mod, gpu, kind, n):
     assert np.array_equal(di, hi)
 
 
+def check_device_equals_host(rtx_mod, name, b):
+    hn, hi = rtx_mod.bvh_build(b, on="host")
+    dn, di = rtx_mod.bvh_build(b, on="gpu")
+    assert len(dn) == len(hn), f"{name}: {len(dn)} device nodes, {len(hn)} host nodes"
+    assert dn.tobytes() == hn.tobytes(), f"{name}: node bytes differ, first at node {first_difference(dn, hn)}"
+    assert np.array_equal(di, hi), f"{name}: prim_indices differ"
+
+
+def first_difference(a, b):
+    return next((i for i in range(len(a)) if a[i:i + 1].tobytes() != b[i:i + 1].tobytes()), None)
+
+
+def family_params(fam):
+    return [pytest.param(name, b, id=name) for name, b in cases.family(fam)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,b", family_params("root_sizes"))
+def test_device_build_root_sizes(rtx_mod, gpu, name, b):
+    """Root ranges of 5 .. 1025: below, at and above one wave (64) and one to four chunks (256)."""
+    check_device_equals_host(rtx_mod, name, b)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,b", family_params("partition_T"))
+def test_device_build_partition_T(rtx_mod, gpu, name, b):
+    """The root's partition with T = 1 .. n - 1 on the left, unswapped, fully swapped, alternating."""
+    check_device_equals_host(rtx_mod, name, b)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,b", family_params("cost_ties"))
+def test_device_build_cost_ties(rtx_mod, gpu, name, b):
+    check_device_equals_host(rtx_mod, name, b)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,b", family_params("axis_ties"))
+def test_device_build_axis_ties(rtx_mod, gpu, name, b):
+    check_device_equals_host(rtx_mod, name, b)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,b", family_params("bin_edges"))
+def test_device_build_bin_edges(rtx_mod, gpu, name, b):
+    check_device_equals_host(rtx_mod, name, b)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,b", family_params("signed_zero_positions"))
+def test_device_build_signed_zero_positions(rtx_mod, gpu, name, b):
+    check_device_equals_host(rtx_mod, name, b)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,b", family_params("chains"))
+def test_device_build_chains(rtx_mod, gpu, name, b):
+    check_device_equals_host(rtx_mod, name, b)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,b", family_params("magnitudes"))
+def test_device_build_magnitudes(rtx_mod, gpu, name, b):
+    """Includes the centroid extents below 2^-1024 (1 / extent = inf): before the explicit bin
+    rule (rtx_bounds.h sah_bin) the device's saturating conversion sent inf to bin 15 and split
+    a root that the host and the reference leave a leaf."""
+    check_device_equals_host(rtx_mod, name, b)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,b", family_params("odd_boxes"))
+def test_device_build_odd_boxes(rtx_mod, gpu, name, b):
+    check_device_equals_host(rtx_mod, name, b)
+
+
 @pytest.mark.gpu
 def test_device_build_empty_and_errors(rtx_mod, gpu):
     n, i = rtx_mod.bvh_build(np.zeros((0, 6)), on="gpu")
     assert len(n) == 0 and len(i) == 0
+    lib = rtx_mod.lib()
+    b = np.ascontiguousarray(cases.root_sizes()[0][1])
+    nodes = np.zeros(2 * len(b), rtx_mod.NODE_DTYPE)
+    idx = np.zeros(len(b), np.uint32)
+    nn = ctypes.c_int64(-7)
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    calls = {
+        "NULL bounds, n > 0": (0, None, len(b), vp(nodes), ctypes.byref(nn), vp(idx)),
+        "NULL out_nodes": (0, vp(b), len(b), None, ctypes.byref(nn), vp(idx)),
+        "NULL out_n_nodes": (0, vp(b), len(b), vp(nodes), None, vp(idx)),
+        "NULL out_prim_indices": (0, vp(b), len(b), vp(nodes), ctypes.byref(nn), None),
+        "n < 0": (0, vp(b), -1, vp(nodes), ctypes.byref(nn), vp(idx)),
+    }
+    for what, args in calls.items():
+        assert lib.rtx_bvh_build(*args) == -1, what  # RTX_ERR_INVALID
+        assert lib.rtx_last_error().decode().startswith("rtx_bvh_build: "), what
+        assert lib.rtx_bvh_build_host(*args[1:]) == -1, what
+        assert len(lib.rtx_last_error()) > 0, what
+    assert nn.value == -7 and not nodes.view(np.uint8).any() and not idx.any()  # a refused call writes nothing
+    dn, di = rtx_mod.bvh_build(b, on="gpu")  # ... and the builder still works afterwards
+    assert len(dn) > 1 and sorted(di.tolist()) == list(range(len(b)))
