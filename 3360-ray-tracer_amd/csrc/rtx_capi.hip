@@ -1447,14 +1447,6 @@ static int render_device_impl(rtx_scene* sc, const rtx_camera* cam, const rtx_re
   // per-launch timing of the dominant kernel (extend / persistent) with an event pool: one
   // pair per hot launch of the whole frame (grow-only pool)
   size_t evi = 0;
-  auto ev_at = [&](size_t i) -> hipEvent_t {
-    while (sc->evpool.size() <= i) {
-      hipEvent_t e = nullptr;
-      if (hipEventCreate(&e) != hipSuccess) return nullptr;
-      sc->evpool.push_back(e);
-    }
-    return sc->evpool[i];
-  };
   const bool timed = stats != nullptr;
   double hot_ms = 0;
   uint64_t hot_launches = 0;
@@ -1486,7 +1478,7 @@ static int render_device_impl(rtx_scene* sc, const rtx_camera* cam, const rtx_re
   if (phased) {
     if ((rc = render_adaptive(sc, L, A, prm, px, budget, other, s, [&](hipStream_t st) -> int {
            if (timed) {
-             hipEvent_t e = ev_at(evi++);
+             hipEvent_t e = sc->pool_event(evi++);
              if (!e) return fail(RTX_ERR_HIP, "hipEventCreate failed");
              HIPC(hipEventRecord(e, st));
            }
@@ -1522,7 +1514,7 @@ static int render_device_impl(rtx_scene* sc, const rtx_camera* cam, const rtx_re
     A.s0 = s0;
     auto hot_begin = [&]() -> int {
       if (timed) {
-        hipEvent_t e = ev_at(evi++);
+        hipEvent_t e = sc->pool_event(evi++);
         if (!e) return fail(RTX_ERR_HIP, "hipEventCreate failed");
         HIPC(hipEventRecord(e, s));
       }
@@ -1599,11 +1591,7 @@ static int render_device_impl(rtx_scene* sc, const rtx_camera* cam, const rtx_re
     HIPC(hipEventElapsedTime(&ms, sc->ev[0], sc->ev[1]));
     // the hot launches' event pairs are read only now: no host wait inside the frame, so the
     // accumulate / resolve launches are queued while the hot kernel still runs
-    for (size_t e = 0; e + 1 < evi; e += 2) {
-      float hms = 0;
-      HIPC(hipEventElapsedTime(&hms, sc->evpool[e], sc->evpool[e + 1]));
-      hot_ms += hms;
-    }
+    if ((rc = sc->pool_pairs_ms(evi, hot_ms))) return rc;
     unsigned long long h[24];
     std::memcpy(h, sc->counters_h.p, sizeof h);
     static const bool drain_debug = std::getenv("RTX_DEBUG_DRAIN") != nullptr;

@@ -2,7 +2,8 @@
 // surface points (rtx_direct*, rtx_scene_emitters, include/rtx.h; DESIGN.md §4g "Direct-lighting
 // queries").  Included once, by rtx_queries.hip, after rtx_irradiance.h.  Nothing here is used by a
 // render kernel, and trace<>(), shade*, k_radiance*, k_irradiance, k_ao and k_occluded are as
-// they were: the kernels below call the same device functions.
+// they were: the kernels below call the same device functions, and k_direct decodes and writes its
+// slot with rtx_radiance.h's chunk_slot and slot_write.
 //
 // Contract: a surfel is an rtx_ray whose origin is the point x and whose direction is the surface
 // normal (any positive finite length).  Sample k of surfel i is direct_sample() of (seed, pixel,
@@ -191,35 +192,32 @@ __global__ __launch_bounds__(kBlock, kTraceWaves) void k_direct(DScene S, Emitte
   uint32_t* stk = lds + threadIdx.x;
   const uint32_t j = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
   if (j >= A.slots) return;
-  const uint32_t r = j / A.K, k = j - r * A.K;
-  const int64_t i = A.ray0 + (int64_t)r;
-  const rtx_ray surfel = A.rays[i];
-  const uint32_t pix = A.ids ? A.ids[i] : (uint32_t)(A.id_base + (uint64_t)i);
-  const uint32_t smp = (uint32_t)A.s0 + k;
-  double* Lp = A.L + 3 * (uint64_t)j;
+  rtx_ray surfel;
+  uint32_t pix, smp;
+  chunk_slot(A, j, surfel, pix, smp);
   V3 o, d, C;
   uint32_t vis = 0u;
   if (direct_sample(S, E, A.seed, pix, smp, surfel, o, d, C))
     vis = occluded<STACK, FAST>(S, o, d, (double)RTX_SEAM_TMIN, kDirectTmax, stk) ? 0u : 1u;
   if (!vis) C = v3(0.0, 0.0, 0.0);
-  Lp[0] = C.x, Lp[1] = C.y, Lp[2] = C.z;
-  A.segs[j] = vis;
+  slot_write(A.L, A.segs, j, C, vis);
 }
 
-// Test hook (rtx_internal_direct_samples): the samples k_direct draws, one lane per (surfel,
-// sample), surfel major, from direct_sample(); 9 doubles per sample (segment origin, y - x, C),
-// all zero where nothing is traced.
-__global__ __launch_bounds__(kBlock) void k_direct_samples(DScene S, EmitterTable E,
-                                                           const rtx_ray* __restrict__ surfels,
-                                                           const uint32_t* __restrict__ ids, uint32_t nslots,
-                                                           uint32_t K, uint64_t seed, int32_t s0,
-                                                           double* __restrict__ out) {
+// Test hook (rtx_internal_direct_samples, rtx_internal_nee_samples): the samples of `stream`, one
+// lane per (surfel, sample), surfel major, from direct_sample_from(): with kRngStreamDirect the
+// samples k_direct draws, with kRngStreamNee + depth those nee_path (rtx_nee.h) draws at a vertex
+// of that depth.  9 doubles per sample (segment origin, y - x, C), all zero where nothing is traced.
+__global__ __launch_bounds__(kBlock) void k_emitter_samples(DScene S, EmitterTable E,
+                                                            const rtx_ray* __restrict__ surfels,
+                                                            const uint32_t* __restrict__ ids, uint32_t nslots,
+                                                            uint32_t K, uint64_t seed, int32_t s0, uint32_t stream,
+                                                            double* __restrict__ out) {
   const uint32_t j = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
   if (j >= nslots) return;
   const uint32_t i = j / K, k = j - i * K;
   const rtx_ray surfel = surfels[i];
   V3 o, d, C;
-  direct_sample(S, E, seed, ids ? ids[i] : i, (uint32_t)s0 + k, surfel, o, d, C);
+  direct_sample_from(S, E, seed, ids ? ids[i] : i, (uint32_t)s0 + k, stream, surfel, o, d, C);
   double* q = out + 9 * (uint64_t)j;
   q[0] = o.x, q[1] = o.y, q[2] = o.z, q[3] = d.x, q[4] = d.y, q[5] = d.z, q[6] = C.x, q[7] = C.y, q[8] = C.z;
 }

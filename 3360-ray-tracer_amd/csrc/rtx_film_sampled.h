@@ -1,12 +1,12 @@
 // rtx_film_sampled.h — films for the light-sampling estimators (rtx_film_create_sampled,
 // include/rtx.h; DESIGN.md §4j "Sampled films"): the frames of rtx_render_nee / rtx_render_mis
 // kept as a film, fixed spp or with the reference's per-pixel adaptive sampling.
-// Included once, by rtx_queries.hip, after rtx_nee.h.  nee_path, nee_slot and every kernel that
-// existed are as they were: the path kernel below calls the same device functions.
+// Included once, by rtx_queries.hip, after rtx_nee.h.  The path kernel below is the frame form of
+// k_sampled (rtx_nee.h) behind the active list: the same camera_slot, nee_path and slot_write.
 //
-// Contract: sample k of subset pixel i has the value of the k_render_nee / k_render_mis slot of
-// (seed, global pixel index, sample k): get_ray on stream 0, nee_path<.., MIS>, sum + L_end.  A
-// fixed film adds its samples to `sum` in sample order from 0; an adaptive film records them in
+// Contract: sample k of subset pixel i has the value of the k_sampled<.., CAMERA = true, MIS> slot of
+// (seed, global pixel index, sample k): camera_slot (get_ray on stream 0), nee_path<.., MIS>,
+// sum + L_end.  A fixed film adds its samples to `sum` in sample order from 0; an adaptive film records them in
 // sample order with k_accumulate's arithmetic (RecordSample, then IsConverged from min_spp on) and
 // stops a pixel at its first converged sample or at the budget; a sample traced past that point is
 // discarded.  Work is done in groups: G samples of every entry of an active list of subset indices
@@ -45,7 +45,8 @@ __device__ __forceinline__ bool film_entry(const FilmGroup& A, uint32_t e, uint3
   return p < A.npix;
 }
 
-// One lane per slot, k_render_nee's launch shape and nee_slot's body for the slot's (pixel, sample).
+// One lane per slot, k_sampled's launch shape and its camera-form body for the slot's (pixel, sample);
+// a kernel of its own because the pixel comes through the active list.
 template <int STACK, bool FAST, bool MIS>
 __global__ __launch_bounds__(kBlock, kTraceWaves) void k_film_paths(DScene S, EmitterTable E, NeeCamera cam,
                                                                     FilmGroup A) {
@@ -57,21 +58,17 @@ __global__ __launch_bounds__(kBlock, kTraceWaves) void k_film_paths(DScene S, Em
   uint32_t i;
   if (!film_entry(A, A.e0 + r, i)) return;
   const uint32_t smp = (uint32_t)A.s0 + k;
-  int x, y;
-  cam.map.xy(i, x, y);
-  const uint32_t pix = (uint32_t)(y * cam.map.W + x);
-  Rng g = make_rng(A.seed, pix, smp, 0u);
+  uint32_t pix;
   V3 o, d;
-  get_ray(cam.cam, x, y, g, o, d);
+  camera_slot(cam, A.seed, i, smp, pix, o, d);
   const NeePath p = nee_path<STACK, FAST, MIS>(S, E, A.seed, pix, smp, A.max_depth, o, d, stk, NeeNoRecord{});
-  const V3 L = p.sum + p.L_end;
-  double* Lp = A.L + 3 * (uint64_t)j;
-  Lp[0] = L.x, Lp[1] = L.y, Lp[2] = L.z;
-  A.segs[j] = p.closest + p.shadow;
+  slot_write(A.L, A.segs, j, p.sum + p.L_end, p.closest + p.shadow);
 }
 
 // Counters every wave of a launch adds to: spread over kFilmSpread words kFilmSpreadStride words
-// apart, as spread_add's are (rtx_frame_kernels.h); k_film_totals sums them.
+// apart, as spread_add's are (rtx_frame_kernels.h); k_film_totals sums them.  (spread_add counts a
+// wave's non-zero lanes with a ballot, film_spread_sum adds the lanes' 64-bit values: two reductions,
+// so the two keep their own definitions, and the frame kernels' header is not this unit's.)
 constexpr int kFilmSpread = 64, kFilmSpreadStride = 16;
 constexpr int kFilmCtrTraced = 0, kFilmCtrRecorded = kFilmSpread * kFilmSpreadStride,
               kFilmCtrTotals = 2 * kFilmSpread * kFilmSpreadStride,  // traced, recorded

@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "rtx.h"
@@ -177,7 +178,24 @@ struct rtx_scene {
   // ev[0] / ev[1]: a timed render's start and end (rtx_stats.kernel_ms), ev[2] / ev[3]: the
   // adaptive debug timing, ev[4]: the frame and its output copy done (the host's wait)
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  // the hot launches' timing events of a timed call: a grow-only pool, used in pairs
   std::vector<hipEvent_t> evpool;
+  hipEvent_t pool_event(size_t i) {  // event i, created on demand; nullptr: hipEventCreate failed
+    while (evpool.size() <= i) {
+      hipEvent_t e = nullptr;
+      if (hipEventCreate(&e) != hipSuccess) return nullptr;
+      evpool.push_back(e);
+    }
+    return evpool[i];
+  }
+  int pool_pairs_ms(size_t n, double& ms) const {  // the sum of the first n / 2 pairs, in ms, added to `ms`
+    for (size_t e = 0; e + 1 < n; e += 2) {
+      float pair_ms = 0;
+      HIPC(hipEventElapsedTime(&pair_ms, evpool[e], evpool[e + 1]));
+      ms += pair_ms;
+    }
+    return RTX_OK;
+  }
   // banded output copies (BandSink): a copy stream and its ordering events
   hipStream_t copy_stream = nullptr;
   std::vector<hipEvent_t> band_ev;
@@ -277,6 +295,11 @@ template <class F>
 int with_walk(const rtx_scene* sc, int32_t precision, F&& f) {
   const bool fast = precision == RTX_PREC_FAST && sc->fast_ok;
   return with_walk(fast ? sc->stack_fast : sc->stack_parity, fast, f);
+}
+// f(std::bool_constant<b>{}): a run-time flag as a kernel's template argument
+template <class F>
+int with_flag(bool b, F&& f) {
+  return b ? f(std::true_type{}) : f(std::false_type{});
 }
 // One lane per item, blocks of kBlock, on `s`
 template <class K, class... Args>

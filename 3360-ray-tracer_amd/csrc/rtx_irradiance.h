@@ -34,24 +34,20 @@ __device__ __forceinline__ bool irradiance_ray(uint64_t seed, uint32_t pix, uint
 
 // One lane per slot of the chunk (RadianceChunk: `rays` are the surfels): slot j is sample
 // s0 + j % K of surfel ray0 + j / K, so a wave's 64 paths start at 64 / K neighbouring points.
-// The whole path per lane, the traversal stack in the lane's LDS column, as in k_radiance; a
-// degenerate surfel's lanes write 0 and leave.
+// The whole path per lane, the traversal stack in the lane's LDS column, as in k_radiance (the
+// same loop text, the same chunk_slot and slot_write); a degenerate surfel's lanes write 0 and leave.
 template <int STACK, bool FAST>
 __global__ __launch_bounds__(kBlock, kTraceWaves) void k_irradiance(DScene S, RadianceChunk A) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   uint32_t* stk = lds + threadIdx.x;
   const uint32_t j = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
   if (j >= A.slots) return;
-  const uint32_t r = j / A.K, k = j - r * A.K;
-  const int64_t i = A.ray0 + (int64_t)r;
-  const rtx_ray surfel = A.rays[i];
-  const uint32_t pix = A.ids ? A.ids[i] : (uint32_t)(A.id_base + (uint64_t)i);
-  const uint32_t smp = (uint32_t)A.s0 + k;
-  double* Lp = A.L + 3 * (uint64_t)j;
+  rtx_ray surfel;
+  uint32_t pix, smp;
+  chunk_slot(A, j, surfel, pix, smp);
   Path P;
   if (!irradiance_ray(A.seed, pix, smp, surfel, P.o, P.d)) {
-    Lp[0] = 0.0, Lp[1] = 0.0, Lp[2] = 0.0;
-    A.segs[j] = 0u;
+    slot_write(A.L, A.segs, j, v3(0.0, 0.0, 0.0), 0u);
     return;
   }
   P.thr = v3(1.0, 1.0, 1.0);
@@ -68,8 +64,7 @@ __global__ __launch_bounds__(kBlock, kTraceWaves) void k_irradiance(DScene S, Ra
     Rng g = make_rng(A.seed, pix, smp, (uint32_t)P.depth + 1u);
     if (!shade(S, A.max_depth, P, h, best >= 0, g, L)) break;
   }
-  Lp[0] = L.x, Lp[1] = L.y, Lp[2] = L.z;
-  A.segs[j] = segs;
+  slot_write(A.L, A.segs, j, L, segs);
 }
 
 // Test hook (rtx_internal_irradiance_rays): the depth-0 segments k_irradiance traces, one lane

@@ -2,7 +2,8 @@
 // (rtx_radiance_nee*, rtx_render_nee*, include/rtx.h; DESIGN.md §4h "Next-event estimation").
 // Included once, by rtx_queries.hip, after rtx_direct.h.  Nothing here is used by a render kernel,
 // and trace<>(), shade*, occluded<>(), k_radiance*, k_direct* are as they were: the kernels below
-// call the same device functions.
+// call the same device functions, and decode and write their slots with rtx_radiance.h's
+// chunk_slot / chunk_index and slot_write.
 //
 // Contract: the path of (seed, pixel, sample) is k_radiance's path: per segment trace<> on
 // ((double)0.001f, +inf), finish_hit<false>, then shade_core / shade_finish (the two halves of
@@ -27,8 +28,8 @@
 // (DESIGN.md §4g): after a diffuse vertex it is neither sampled nor counted.
 //
 // The same path with multiple importance sampling (rtx_radiance_mis*, rtx_render_mis*)
-// is nee_path<.., MIS = true>: its contract stands at nee_path below.  Every kernel that existed is
-// the MIS = false path.
+// is nee_path<.., MIS = true>: its contract stands at nee_path below.  One kernel, k_sampled, runs
+// the path for both estimators, on rays and on the camera's frame.
 #pragma once
 
 #include "rtx_direct.h"
@@ -51,10 +52,9 @@ struct NeePath {
   uint32_t closest, shadow;
 };
 
-// The kernels' recorder: nothing is kept per vertex.
+// The kernels' recorder: nothing is kept per vertex (the last two arguments are the MIS form's).
 struct NeeNoRecord {
-  __device__ __forceinline__ void operator()(int32_t, const Hit&, bool, V3, uint32_t) const {}
-  __device__ __forceinline__ void operator()(int32_t, const Hit&, bool, V3, uint32_t, double, double) const {}  // (MIS)
+  __device__ __forceinline__ void operator()(int32_t, const Hit&, bool, V3, uint32_t, double = 0.0, double = 0.0) const {}
 };
 
 // Is `prim` (an index of the device primitive array) in the emitter table?  E.prim is ascending
@@ -186,159 +186,89 @@ struct NeeCamera {
   rtx_camera cam;
   PixelMap map;
 };
+// Sample smp of subset pixel i: the global pixel key and the depth-0 segment (the one definition of
+// the camera form, k_sampled<.., CAMERA = true> and k_film_paths).
+__device__ __forceinline__ void camera_slot(const NeeCamera& C, uint64_t seed, uint32_t i, uint32_t smp, uint32_t& pix,
+                                            V3& o, V3& d) {
+  int x, y;
+  C.map.xy(i, x, y);
+  pix = (uint32_t)(y * C.map.W + x);
+  Rng g = make_rng(seed, pix, smp, 0u);
+  get_ray(C.cam, x, y, g, o, d);
+}
 
-template <int STACK, bool FAST, bool CAMERA, bool MIS = false>
-__device__ __forceinline__ void nee_slot(const DScene& S, const EmitterTable& E, const RadianceChunk& A,
-                                         const NeeCamera* cam, uint32_t* stk) {
+// The sampled path's one query kernel: one lane per slot, k_radiance's launch shape, the whole path
+// with its emitter samples, the traversal stack (of the closest-hit walk and, between two of them,
+// of the any-hit walk) in the lane's LDS column.  CAMERA = false: the caller's rays
+// (rtx_radiance_nee*, rtx_radiance_mis*; `cam` is not read).  CAMERA = true: the frame form, the
+// same body from the camera's own depth-0 segments (rtx_render_nee*, rtx_render_mis*; A.rays and
+// A.ids are not read, A.ray0 counts pixels of the subset).  MIS: nee_path's power-heuristic form.
+template <int STACK, bool FAST, bool CAMERA, bool MIS>
+__global__ __launch_bounds__(kBlock, kTraceWaves) void k_sampled(DScene S, EmitterTable E, RadianceChunk A,
+                                                                 NeeCamera cam) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  uint32_t* stk = lds + threadIdx.x;
   const uint32_t j = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
   if (j >= A.slots) return;
-  const uint32_t r = j / A.K, k = j - r * A.K;
-  const int64_t i = A.ray0 + (int64_t)r;
-  const uint32_t smp = (uint32_t)A.s0 + k;
-  uint32_t pix;
+  uint32_t pix, smp;
   V3 o, d;
   if (CAMERA) {
-    int x, y;
-    cam->map.xy((uint32_t)i, x, y);
-    pix = (uint32_t)(y * cam->map.W + x);
-    Rng g = make_rng(A.seed, pix, smp, 0u);
-    get_ray(cam->cam, x, y, g, o, d);
+    int64_t i;
+    uint32_t k;
+    chunk_index(A, j, i, k);
+    smp = (uint32_t)A.s0 + k;
+    camera_slot(cam, A.seed, (uint32_t)i, smp, pix, o, d);
   } else {
-    const rtx_ray ray = A.rays[i];
-    pix = A.ids ? A.ids[i] : (uint32_t)(A.id_base + (uint64_t)i);
+    rtx_ray ray;
+    chunk_slot(A, j, ray, pix, smp);
     o = v3(ray.origin[0], ray.origin[1], ray.origin[2]);
     d = v3(ray.direction[0], ray.direction[1], ray.direction[2]);
   }
   const NeePath p = nee_path<STACK, FAST, MIS>(S, E, A.seed, pix, smp, A.max_depth, o, d, stk, NeeNoRecord{});
-  const V3 L = p.sum + p.L_end;
-  double* Lp = A.L + 3 * (uint64_t)j;
-  Lp[0] = L.x, Lp[1] = L.y, Lp[2] = L.z;
-  A.segs[j] = p.closest + p.shadow;
+  slot_write(A.L, A.segs, j, p.sum + p.L_end, p.closest + p.shadow);
 }
 
-// One lane per slot, k_radiance's launch shape: the whole path with its emitter samples, the
-// traversal stack (of the closest-hit walk and, between two of them, of the any-hit walk) in the
-// lane's LDS column.
-template <int STACK, bool FAST>
-__global__ __launch_bounds__(kBlock, kTraceWaves) void k_radiance_nee(DScene S, EmitterTable E, RadianceChunk A) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-  nee_slot<STACK, FAST, false>(S, E, A, nullptr, lds + threadIdx.x);
-}
-// The frame form: the same body from the camera's own depth-0 segments (A.rays and A.ids are not
-// read; A.ray0 counts pixels of the subset).
-template <int STACK, bool FAST>
-__global__ __launch_bounds__(kBlock, kTraceWaves) void k_render_nee(DScene S, EmitterTable E, RadianceChunk A,
-                                                                    NeeCamera cam) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-  nee_slot<STACK, FAST, true>(S, E, A, &cam, lds + threadIdx.x);
-}
-
-// The MIS forms of the two (nee_path<.., MIS = true>): the same launch shape, arguments and slots.
-template <int STACK, bool FAST>
-__global__ __launch_bounds__(kBlock, kTraceWaves) void k_radiance_mis(DScene S, EmitterTable E, RadianceChunk A) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-  nee_slot<STACK, FAST, false, true>(S, E, A, nullptr, lds + threadIdx.x);
-}
-template <int STACK, bool FAST>
-__global__ __launch_bounds__(kBlock, kTraceWaves) void k_render_mis(DScene S, EmitterTable E, RadianceChunk A,
-                                                                    NeeCamera cam) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-  nee_slot<STACK, FAST, true, true>(S, E, A, &cam, lds + threadIdx.x);
-}
-
-// Test hook (rtx_internal_nee_samples): k_direct_samples on stream kRngStreamNee + depth, the
-// samples nee_path draws at a vertex of that depth, from direct_sample_from(); 9 doubles per
-// sample (segment origin, y - x, C), all zero where nothing is traced.
-__global__ __launch_bounds__(kBlock) void k_nee_samples(DScene S, EmitterTable E, const rtx_ray* __restrict__ surfels,
-                                                        const uint32_t* __restrict__ ids, uint32_t nslots, uint32_t K,
-                                                        uint64_t seed, int32_t s0, uint32_t depth,
-                                                        double* __restrict__ out) {
-  const uint32_t j = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
-  if (j >= nslots) return;
-  const uint32_t i = j / K, k = j - i * K;
-  const rtx_ray surfel = surfels[i];
-  V3 o, d, C;
-  direct_sample_from(S, E, seed, ids ? ids[i] : i, (uint32_t)s0 + k, kRngStreamNee + depth, surfel, o, d, C);
-  double* q = out + 9 * (uint64_t)j;
-  q[0] = o.x, q[1] = o.y, q[2] = o.z, q[3] = d.x, q[4] = d.y, q[5] = d.z, q[6] = C.x, q[7] = C.y, q[8] = C.z;
-}
-
-// Test hook (rtx_internal_nee_trace): nee_path with a recorder.  Per slot and per segment below
-// `cap`, 9 doubles (the vertex point, the shading normal, w; zero on a miss, w zero where no term
-// is eligible) into verts and the flag word into flags; per slot L_end (3 doubles) into ends and
-// the closest-hit and shadow segment counts into counts.  Records past the path's end are not
-// written (the host zeroes the buffers).
+// Test hook (rtx_internal_nee_trace, rtx_internal_mis_trace): nee_path with a recorder.  Per slot
+// and per segment below `cap`, kDoubles doubles into verts and the flag word into flags: the vertex
+// point, the shading normal, w (zero on a miss, w zero where no term is eligible), and with MIS g of
+// the vertex's light sample (0 where none was traceable) and the gb applied to the segment's
+// emission (0 where none applied): 9 or 11.  Per slot L_end (3 doubles) into ends and the
+// closest-hit and shadow segment counts into counts.  Records past the path's end are not written
+// (the host zeroes the buffers).
+template <bool MIS>
 struct NeeRecorder {
+  static constexpr int kDoubles = MIS ? 11 : 9;
   double* verts;
   uint32_t* flags;
   int32_t cap;
-  __device__ __forceinline__ void operator()(int32_t depth, const Hit& h, bool hit, V3 w, uint32_t f) const {
+  __device__ __forceinline__ void operator()(int32_t depth, const Hit& h, bool hit, V3 w, uint32_t f, double g = 0.0,
+                                             double gb = 0.0) const {
     if (depth >= cap) return;
-    double* q = verts + 9 * depth;
+    double* q = verts + kDoubles * depth;
     if (hit) q[0] = h.p.x, q[1] = h.p.y, q[2] = h.p.z, q[3] = h.normal.x, q[4] = h.normal.y, q[5] = h.normal.z;
     q[6] = w.x, q[7] = w.y, q[8] = w.z;
+    if (MIS) q[9] = g, q[10] = gb;
     flags[depth] = f;
   }
 };
-template <int STACK, bool FAST>
-__global__ __launch_bounds__(kBlock, kTraceWaves) void k_nee_trace(DScene S, EmitterTable E, RadianceChunk A,
-                                                                   int32_t cap, double* __restrict__ verts,
-                                                                   uint32_t* __restrict__ flags,
-                                                                   double* __restrict__ ends,
-                                                                   uint32_t* __restrict__ counts) {
+template <int STACK, bool FAST, bool MIS>
+__global__ __launch_bounds__(kBlock, kTraceWaves) void k_path_trace(DScene S, EmitterTable E, RadianceChunk A,
+                                                                    int32_t cap, double* __restrict__ verts,
+                                                                    uint32_t* __restrict__ flags,
+                                                                    double* __restrict__ ends,
+                                                                    uint32_t* __restrict__ counts) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   uint32_t* stk = lds + threadIdx.x;
   const uint32_t j = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
   if (j >= A.slots) return;
-  const uint32_t r = j / A.K, k = j - r * A.K;
-  const int64_t i = A.ray0 + (int64_t)r;
-  const rtx_ray ray = A.rays[i];
-  const uint32_t pix = A.ids ? A.ids[i] : (uint32_t)(A.id_base + (uint64_t)i);
-  const NeeRecorder rec{verts + 9 * (uint64_t)j * (uint64_t)cap, flags + (uint64_t)j * (uint64_t)cap, cap};
-  const NeePath p = nee_path<STACK, FAST>(S, E, A.seed, pix, (uint32_t)A.s0 + k, A.max_depth,
-                                          v3(ray.origin[0], ray.origin[1], ray.origin[2]),
-                                          v3(ray.direction[0], ray.direction[1], ray.direction[2]), stk, rec);
-  double* e = ends + 3 * (uint64_t)j;
-  e[0] = p.L_end.x, e[1] = p.L_end.y, e[2] = p.L_end.z;
-  counts[2 * (uint64_t)j] = p.closest, counts[2 * (uint64_t)j + 1] = p.shadow;
-}
-
-
-// Test hook (rtx_internal_mis_trace): k_nee_trace for the MIS form.  11 doubles per segment: the
-// nine of NeeRecorder, then g of the vertex's light sample (0 where none was traceable) and the gb
-// applied to the segment's emission (0 where none applied).
-struct MisRecorder {
-  double* verts;
-  uint32_t* flags;
-  int32_t cap;
-  __device__ __forceinline__ void operator()(int32_t depth, const Hit& h, bool hit, V3 w, uint32_t f, double g,
-                                             double gb) const {
-    if (depth >= cap) return;
-    double* q = verts + 11 * depth;
-    if (hit) q[0] = h.p.x, q[1] = h.p.y, q[2] = h.p.z, q[3] = h.normal.x, q[4] = h.normal.y, q[5] = h.normal.z;
-    q[6] = w.x, q[7] = w.y, q[8] = w.z;
-    q[9] = g, q[10] = gb;
-    flags[depth] = f;
-  }
-};
-template <int STACK, bool FAST>
-__global__ __launch_bounds__(kBlock, kTraceWaves) void k_mis_trace(DScene S, EmitterTable E, RadianceChunk A,
-                                                                   int32_t cap, double* __restrict__ verts,
-                                                                   uint32_t* __restrict__ flags,
-                                                                   double* __restrict__ ends,
-                                                                   uint32_t* __restrict__ counts) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-  uint32_t* stk = lds + threadIdx.x;
-  const uint32_t j = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
-  if (j >= A.slots) return;
-  const uint32_t r = j / A.K, k = j - r * A.K;
-  const int64_t i = A.ray0 + (int64_t)r;
-  const rtx_ray ray = A.rays[i];
-  const uint32_t pix = A.ids ? A.ids[i] : (uint32_t)(A.id_base + (uint64_t)i);
-  const MisRecorder rec{verts + 11 * (uint64_t)j * (uint64_t)cap, flags + (uint64_t)j * (uint64_t)cap, cap};
-  const NeePath p = nee_path<STACK, FAST, true>(S, E, A.seed, pix, (uint32_t)A.s0 + k, A.max_depth,
-                                                v3(ray.origin[0], ray.origin[1], ray.origin[2]),
-                                                v3(ray.direction[0], ray.direction[1], ray.direction[2]), stk, rec);
+  rtx_ray ray;
+  uint32_t pix, smp;
+  chunk_slot(A, j, ray, pix, smp);
+  using Rec = NeeRecorder<MIS>;
+  const Rec rec{verts + Rec::kDoubles * (uint64_t)j * (uint64_t)cap, flags + (uint64_t)j * (uint64_t)cap, cap};
+  const NeePath p = nee_path<STACK, FAST, MIS>(S, E, A.seed, pix, smp, A.max_depth,
+                                               v3(ray.origin[0], ray.origin[1], ray.origin[2]),
+                                               v3(ray.direction[0], ray.direction[1], ray.direction[2]), stk, rec);
   double* e = ends + 3 * (uint64_t)j;
   e[0] = p.L_end.x, e[1] = p.L_end.y, e[2] = p.L_end.z;
   counts[2 * (uint64_t)j] = p.closest, counts[2 * (uint64_t)j + 1] = p.shadow;

@@ -77,6 +77,10 @@ int ao_check(const rtx_scene* sc, const rtx_camera* cam, const rtx_render_params
 // ---- radiance queries (rtx_radiance.h) ----
 // the slot cap of the calls that follow (rtx_internal_radiance_chunk; 0: kRadianceSlots)
 std::atomic<int64_t> g_radiance_chunk{0};
+int64_t slot_cap() {
+  const int64_t tuned = g_radiance_chunk.load();
+  return std::min<int64_t>(tuned > 0 ? tuned : kRadianceSlots, kRadianceSlotsMax);
+}
 // what a chunk's slots hold (radiance_on): a path from a caller's ray, a path from a surfel's
 // hemisphere sample, a surfel's emitter sample, or a path with next-event estimation (from a
 // caller's ray, or from the camera when radiance_on is given one), plain or with MIS weights
@@ -100,14 +104,13 @@ int radiance_check(const rtx_scene* sc, const rtx_radiance_params* prm, const vo
 // null (the host entry point's batches).  what: for kSlotIrradiance and kSlotDirect d_rays are
 // surfels and the slots are k_irradiance's (rtx_irradiance*) or k_direct's (rtx_direct*: a
 // slot's "segments" are its visibility, 0 or 1); the chunking, the scratch and the sum are the same.
-// kSlotNee: k_radiance_nee's slots, or with `cam` k_render_nee's: the "rays" are then the n pixels
-// of the camera's subset in subset order (d_rays and d_ids are not read).  kSlotMis: the same with
-// k_radiance_mis / k_render_mis.
+// kSlotNee, kSlotMis: k_sampled's slots, from the caller's rays or with `cam` from the camera: the
+// "rays" are then the n pixels of the camera's subset in subset order (d_rays and d_ids are not
+// read).
 int radiance_on(rtx_scene* sc, const rtx_ray* d_rays, const uint32_t* d_ids, uint64_t id_base, int64_t n,
                 const rtx_radiance_params* prm, double* d_out, uint32_t* d_segs, hipStream_t s,
                 SlotKind what = kSlotRadiance, const NeeCamera* cam = nullptr) {
-  const int64_t tuned = g_radiance_chunk.load();
-  const int64_t cap = std::min<int64_t>(tuned > 0 ? tuned : kRadianceSlots, kRadianceSlotsMax);
+  const int64_t cap = slot_cap();
   const int64_t spp = prm->spp;
   const int64_t rays_per = std::max<int64_t>(1, cap / spp);  // rays per chunk
   const int64_t k_per = std::min<int64_t>(spp, cap);         // samples of a ray per chunk
@@ -119,8 +122,11 @@ int radiance_on(rtx_scene* sc, const rtx_ray* d_rays, const uint32_t* d_ids, uin
     if ((rc = sc->rad_carry.reserve(4 * sizeof(double)))) return rc;
   }
   double* const carry = k_per < spp ? sc->rad_carry.as<double>() : nullptr;
+  const EmitterTable E = emitter_table(sc);
+  const NeeCamera nc = cam ? *cam : NeeCamera{};  // (k_sampled's ray form takes one and does not read it)
   return with_walk(sc, prm->precision, [&](auto w) {
-    constexpr size_t lds = stack_lds_bytes(w.stack);
+    using W = decltype(w);
+    constexpr size_t lds = stack_lds_bytes(W::stack);
     for (int64_t r0 = 0; r0 < n; r0 += rays_per) {
       const int64_t nr = std::min<int64_t>(rays_per, n - r0);
       for (int64_t k0 = 0; k0 < spp; k0 += k_per) {
@@ -130,19 +136,16 @@ int radiance_on(rtx_scene* sc, const rtx_ray* d_rays, const uint32_t* d_ids, uin
         A.slots = (uint32_t)(nr * K), A.K = (uint32_t)K;
         A.s0 = (int32_t)(prm->first_sample + k0), A.max_depth = prm->max_depth, A.seed = prm->seed;
         A.L = sc->rad_L.as<double>(), A.segs = sc->rad_segs.as<uint32_t>();
-        switch (what) {
-          case kSlotDirect: rc = launch_1d(k_direct<w.stack, w.fast>, A.slots, lds, s, sc->S, emitter_table(sc), A); break;
-          case kSlotIrradiance: rc = launch_1d(k_irradiance<w.stack, w.fast>, A.slots, lds, s, sc->S, A); break;
-          case kSlotNee:
-            if (cam) rc = launch_1d(k_render_nee<w.stack, w.fast>, A.slots, lds, s, sc->S, emitter_table(sc), A, *cam);
-            else rc = launch_1d(k_radiance_nee<w.stack, w.fast>, A.slots, lds, s, sc->S, emitter_table(sc), A);
-            break;
-          case kSlotMis:
-            if (cam) rc = launch_1d(k_render_mis<w.stack, w.fast>, A.slots, lds, s, sc->S, emitter_table(sc), A, *cam);
-            else rc = launch_1d(k_radiance_mis<w.stack, w.fast>, A.slots, lds, s, sc->S, emitter_table(sc), A);
-            break;
-          default: rc = launch_1d(k_radiance<w.stack, w.fast>, A.slots, lds, s, sc->S, A);
-        }
+        if (what == kSlotRadiance) rc = launch_1d(k_radiance<W::stack, W::fast>, A.slots, lds, s, sc->S, A);
+        else if (what == kSlotIrradiance) rc = launch_1d(k_irradiance<W::stack, W::fast>, A.slots, lds, s, sc->S, A);
+        else if (what == kSlotDirect) rc = launch_1d(k_direct<W::stack, W::fast>, A.slots, lds, s, sc->S, E, A);
+        else
+          rc = with_flag(cam != nullptr, [&](auto camera) {
+            return with_flag(what == kSlotMis, [&](auto mis) {
+              return launch_1d(k_sampled<W::stack, W::fast, decltype(camera)::value, decltype(mis)::value>, A.slots,
+                               lds, s, sc->S, E, A, nc);
+            });
+          });
         if (rc) return rc;
         if ((rc = launch_1d(k_radiance_sum, nr, 0, s, sc->rad_L.as<double>(), sc->rad_segs.as<uint32_t>(), nr,
                             (uint32_t)K, k0 == 0 ? 1 : 0, k0 + K == spp ? 1 : 0, prm->spp, carry,
@@ -232,11 +235,14 @@ int surfel_samples(rtx_scene* sc, const rtx_ray* surfels, const uint32_t* ids, s
   return RTX_OK;
 }
 // ---- frames with next-event estimation (rtx_nee.h) ----
-// the checks rtx_render_nee / rtx_render_mis and their _device forms share, in the documented
-// order; *npix: pixels of the subset; rp: the render params read as the radiance family reads its
-// own; mis: the messages say "mis" where the NEE family's say "nee"
-int render_nee_check(const rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, NeeCamera& nc,
-                     int64_t* npix, rtx_radiance_params& rp, bool mis = false) {
+// What rtx_render_nee / rtx_render_mis and their _device forms do first: the checks in the
+// documented order, then the empty subset (*npix == 0: the caller returns RTX_OK), then the output
+// buffer, then the device.  rp: the render params read as the radiance family reads its own; the
+// messages say "mis" where the NEE family's say "nee" (what: kSlotNee or kSlotMis).
+int render_nee_begin(const rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, const void* out,
+                     SlotKind what, NeeCamera& nc, int64_t* npix, rtx_radiance_params& rp) {
+  const bool mis = what == kSlotMis;
+  *npix = 0;
   if (!sc) return fail(RTX_ERR_INVALID, "scene is NULL");
   if (!cam || !prm) return fail(RTX_ERR_INVALID, "NULL argument");
   if (prm->spp < 1)
@@ -252,6 +258,9 @@ int render_nee_check(const rtx_scene* sc, const rtx_camera* cam, const rtx_rende
   std::string err;
   *npix = subset_pixels(cam, prm, nc.map, err);
   if (*npix < 0) return fail(RTX_ERR_INVALID, err);
+  if (*npix == 0) return RTX_OK;
+  if (!out) return fail(RTX_ERR_INVALID, "NULL buffer");
+  HIPC(hipSetDevice(sc->device));
   nc.cam = *cam;
   rp.spp = prm->spp, rp.max_depth = prm->max_depth, rp.first_sample = 0, rp.precision = prm->precision;
   rp.seed = prm->seed;
@@ -264,10 +273,7 @@ int render_nee_device(rtx_scene* sc, const rtx_camera* cam, const rtx_render_par
   int64_t npix;
   rtx_radiance_params rp{};
   int rc;
-  if ((rc = render_nee_check(sc, cam, prm, nc, &npix, rp, what == kSlotMis))) return rc;
-  if (npix == 0) return RTX_OK;
-  if (!d_out_rgb) return fail(RTX_ERR_INVALID, "NULL buffer");
-  HIPC(hipSetDevice(sc->device));
+  if ((rc = render_nee_begin(sc, cam, prm, d_out_rgb, what, nc, &npix, rp)) || npix == 0) return rc;
   return radiance_on(sc, nullptr, nullptr, 0, npix, &rp, d_out_rgb, d_out_segments,
                      stream ? (hipStream_t)stream : sc->stream, what, &nc);
 }
@@ -277,10 +283,7 @@ int render_nee_host(rtx_scene* sc, const rtx_camera* cam, const rtx_render_param
   int64_t npix;
   rtx_radiance_params rp{};
   int rc;
-  if ((rc = render_nee_check(sc, cam, prm, nc, &npix, rp, what == kSlotMis))) return rc;
-  if (npix == 0) return RTX_OK;
-  if (!out_rgb) return fail(RTX_ERR_INVALID, "NULL buffer");
-  HIPC(hipSetDevice(sc->device));
+  if ((rc = render_nee_begin(sc, cam, prm, out_rgb, what, nc, &npix, rp)) || npix == 0) return rc;
   if ((rc = sc->rad_out.reserve((size_t)npix * 3 * sizeof(double)))) return rc;
   if ((rc = sc->rad_oseg.reserve((size_t)npix * sizeof(uint32_t)))) return rc;
   if ((rc = radiance_on(sc, nullptr, nullptr, 0, npix, &rp, sc->rad_out.as<double>(), sc->rad_oseg.as<uint32_t>(),
@@ -293,7 +296,7 @@ int render_nee_host(rtx_scene* sc, const rtx_camera* cam, const rtx_render_param
   return RTX_OK;
 }
 // What rtx_internal_nee_trace and rtx_internal_mis_trace share (per: doubles per recorded segment,
-// 9 or 11; the MIS form launches k_mis_trace and says "mis" in its messages).
+// 9 or 11; the MIS form launches k_path_trace<.., true> and says "mis" in its messages).
 int path_trace_hook(rtx_scene* sc, const rtx_ray* rays, const uint32_t* ids, size_t n, const rtx_radiance_params* prm,
                     int32_t cap, double* verts, uint32_t* flags, double* ends, uint32_t* counts, bool mis) {
   const size_t per = mis ? 11 : 9;
@@ -329,13 +332,14 @@ int path_trace_hook(rtx_scene* sc, const rtx_ray* rays, const uint32_t* ids, siz
   A.rays = sc->rays.as<rtx_ray>(), A.ids = ids ? sc->rad_ids.as<uint32_t>() : nullptr, A.ray0 = 0, A.id_base = 0;
   A.slots = (uint32_t)nslots, A.K = (uint32_t)prm->spp;
   A.s0 = prm->first_sample, A.max_depth = prm->max_depth, A.seed = prm->seed;
-  A.L = nullptr, A.segs = nullptr;  // (not written by k_nee_trace / k_mis_trace)
+  A.L = nullptr, A.segs = nullptr;  // (not written by k_path_trace)
   if ((rc = with_walk(sc, prm->precision, [&](auto w) {
-         if (mis)
-           return launch_1d(k_mis_trace<w.stack, w.fast>, (int64_t)nslots, stack_lds_bytes(w.stack), s, sc->S,
-                            emitter_table(sc), A, cap, d_verts, d_flags, d_ends, d_counts);
-         return launch_1d(k_nee_trace<w.stack, w.fast>, (int64_t)nslots, stack_lds_bytes(w.stack), s, sc->S,
-                          emitter_table(sc), A, cap, d_verts, d_flags, d_ends, d_counts);
+         using W = decltype(w);
+         return with_flag(mis, [&](auto m) {
+           return launch_1d(k_path_trace<W::stack, W::fast, decltype(m)::value>, (int64_t)nslots,
+                            stack_lds_bytes(W::stack), s, sc->S, emitter_table(sc), A, cap, d_verts, d_flags, d_ends,
+                            d_counts);
+         });
        })))
     return rc;
   HIPC(hipMemcpyAsync(verts, d_verts, b_verts, hipMemcpyDeviceToHost, s));
@@ -369,8 +373,7 @@ int film_sampled_render(rtx_film* f, int32_t budget, rtx_stats* stats) {
   HIPC(hipSetDevice(sc->device));
   hipStream_t s = sc->stream;
   const bool mis = f->estimator == RTX_ESTIMATOR_MIS;
-  const int64_t tuned = g_radiance_chunk.load();
-  const int64_t cap = std::min<int64_t>(tuned > 0 ? tuned : kRadianceSlots, kRadianceSlotsMax);
+  const int64_t cap = slot_cap();
   int rc;
   if ((rc = sc->fs_ctr.reserve(kFilmCtrWords * sizeof(unsigned long long)))) return rc;
   if ((rc = sc->fs_host.reserve(4 * sizeof(unsigned long long)))) return rc;
@@ -391,14 +394,6 @@ int film_sampled_render(rtx_film* f, int32_t budget, rtx_stats* stats) {
   // timing: the call between ev[0] and ev[1], each path launch between a pair of the pool
   const bool timed = stats != nullptr;
   size_t evi = 0;
-  auto ev_at = [&](size_t i) -> hipEvent_t {
-    while (sc->evpool.size() <= i) {
-      hipEvent_t e = nullptr;
-      if (hipEventCreate(&e) != hipSuccess) return nullptr;
-      sc->evpool.push_back(e);
-    }
-    return sc->evpool[i];
-  };
   uint64_t slots_traced = 0, hot_launches = 0;
   if (timed) HIPC(hipEventRecord(sc->ev[0], s));
   FilmGroup A{};
@@ -416,15 +411,17 @@ int film_sampled_render(rtx_film* f, int32_t budget, rtx_stats* stats) {
       A.L = sc->rad_L.as<double>(), A.segs = sc->rad_segs.as<uint32_t>();
       hipEvent_t e0 = nullptr, e1 = nullptr;
       if (timed) {
-        e0 = ev_at(evi), e1 = ev_at(evi + 1);
+        e0 = sc->pool_event(evi), e1 = sc->pool_event(evi + 1);
         if (!e0 || !e1) return fail(RTX_ERR_HIP, "hipEventCreate failed");
         evi += 2;
         HIPC(hipEventRecord(e0, s));
       }
       if ((r = with_walk(sc, f->prm.precision, [&](auto wk) {
-             constexpr size_t lds = stack_lds_bytes(wk.stack);
-             if (mis) return launch_1d(k_film_paths<wk.stack, wk.fast, true>, slots, lds, s, sc->S, E, nc, A);
-             return launch_1d(k_film_paths<wk.stack, wk.fast, false>, slots, lds, s, sc->S, E, nc, A);
+             using W = decltype(wk);
+             return with_flag(mis, [&](auto m) {
+               return launch_1d(k_film_paths<W::stack, W::fast, decltype(m)::value>, slots, stack_lds_bytes(W::stack), s,
+                                sc->S, E, nc, A);
+             });
            })))
         return r;
       if (timed) HIPC(hipEventRecord(e1, s));
@@ -491,11 +488,7 @@ int film_sampled_render(rtx_film* f, int32_t budget, rtx_stats* stats) {
     float ms = 0;
     HIPC(hipEventElapsedTime(&ms, sc->ev[0], sc->ev[1]));
     double hot_ms = 0;
-    for (size_t e = 0; e + 1 < evi; e += 2) {
-      float hms = 0;
-      HIPC(hipEventElapsedTime(&hms, sc->evpool[e], sc->evpool[e + 1]));
-      hot_ms += hms;
-    }
+    if ((rc = sc->pool_pairs_ms(evi, hot_ms))) return rc;
     stats->paths = stats->rays_primary = slots_traced;
     stats->rays_total = pin[0], stats->rays_recorded = pin[1];
     stats->kernel_ms = ms, stats->hot_kernel_ms = hot_ms, stats->hot_launches = hot_launches;
@@ -713,14 +706,15 @@ int rtx_scene_emitters(const rtx_scene* sc, int64_t* count, double* area) {
 // Test hook (not in rtx.h): the samples rtx_direct draws for the same arguments (seed,
 // first_sample and spp of prm are read; the rest is checked as there), n x spp x 9 doubles
 // (segment origin, y - x, the unshadowed contribution C), surfel major, made by the device
-// function k_direct calls (direct_sample, rtx_direct.h); all zero where nothing is traced.  Host
+// function k_direct calls (direct_sample, through k_emitter_samples, rtx_direct.h); all zero where nothing is traced.  Host
 // buffers.
 int rtx_internal_direct_samples(rtx_scene* sc, const rtx_ray* surfels, const uint32_t* ids, size_t n,
                                 const rtx_radiance_params* prm, double* out) {
   return surfel_samples(sc, surfels, ids, n, prm, out, 9, "direct samples: too many samples for one call",
                         [&](uint32_t nslots, const rtx_ray* d_surfels, const uint32_t* d_ids, double* d_out) {
-                          return launch_1d(k_direct_samples, nslots, 0, sc->stream, sc->S, emitter_table(sc), d_surfels,
-                                           d_ids, nslots, (uint32_t)prm->spp, prm->seed, prm->first_sample, d_out);
+                          return launch_1d(k_emitter_samples, nslots, 0, sc->stream, sc->S, emitter_table(sc), d_surfels,
+                                           d_ids, nslots, (uint32_t)prm->spp, prm->seed, prm->first_sample,
+                                           kRngStreamDirect, d_out);
                         });
 }
 
@@ -781,22 +775,22 @@ int rtx_render_mis(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params
 }
 
 // Test hook (not in rtx.h): rtx_internal_direct_samples on stream kRngStreamNee + depth, the
-// samples a path of rtx_radiance_nee draws at a vertex of that depth (k_nee_samples, rtx_nee.h);
+// samples a path of rtx_radiance_nee draws at a vertex of that depth (k_emitter_samples, rtx_direct.h);
 // depth outside 0 .. 0x00FFFFFE is RTX_ERR_INVALID after the shared checks.  Host buffers.
 int rtx_internal_nee_samples(rtx_scene* sc, const rtx_ray* surfels, const uint32_t* ids, size_t n,
                              const rtx_radiance_params* prm, int32_t depth, double* out) {
   return surfel_samples(
       sc, surfels, ids, n, prm, out, 9, "nee samples: too many samples for one call",
       [&](uint32_t nslots, const rtx_ray* d_surfels, const uint32_t* d_ids, double* d_out) {
-        return launch_1d(k_nee_samples, nslots, 0, sc->stream, sc->S, emitter_table(sc), d_surfels, d_ids, nslots,
-                         (uint32_t)prm->spp, prm->seed, prm->first_sample, (uint32_t)depth, d_out);
+        return launch_1d(k_emitter_samples, nslots, 0, sc->stream, sc->S, emitter_table(sc), d_surfels, d_ids, nslots,
+                         (uint32_t)prm->spp, prm->seed, prm->first_sample, kRngStreamNee + (uint32_t)depth, d_out);
       },
       depth < 0 || depth >= 0x00FFFFFF ? "nee samples: depth outside 0..16777214" : nullptr);
 }
 
 // Test hook (not in rtx.h): the paths of rtx_radiance_nee for the same rays, keys and params, one
 // slot per (ray, sample), ray major, from the device function its kernel runs (nee_path through
-// k_nee_trace, rtx_nee.h).  Per slot and segment d < cap: verts 9 doubles (vertex point, shading
+// k_path_trace, rtx_nee.h).  Per slot and segment d < cap: verts 9 doubles (vertex point, shading
 // normal, w = thr * rho; zero on a miss, w zero where no term is eligible) and one flag word
 // (1 term eligible, 2 sample traced, 4 visible, 8 the path ended here on an emitter whose emission
 // is suppressed); segments a path does not reach stay zero.  Per slot: ends 3 doubles (L_end) and
@@ -807,8 +801,8 @@ int rtx_internal_nee_trace(rtx_scene* sc, const rtx_ray* rays, const uint32_t* i
   return path_trace_hook(sc, rays, ids, n, prm, cap, verts, flags, ends, counts, false);
 }
 
-// Test hook (not in rtx.h): rtx_internal_nee_trace for the paths of rtx_radiance_mis (k_mis_trace,
-// rtx_nee.h).  verts holds 11 doubles per slot and segment: the nine of rtx_internal_nee_trace,
+// Test hook (not in rtx.h): rtx_internal_nee_trace for the paths of rtx_radiance_mis (k_path_trace's MIS
+// form, rtx_nee.h).  verts holds 11 doubles per slot and segment: the nine of rtx_internal_nee_trace,
 // then g of the vertex's light sample (0 where none was traceable) and the gb applied to the
 // segment's emission (0 where none applied).  Flag 8 is never set; 16: the path ended here on an
 // emitter of the table and its emission was weighted with gb.  Messages say "mis".

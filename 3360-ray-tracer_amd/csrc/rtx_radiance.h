@@ -1,7 +1,11 @@
 // rtx_radiance.h — radiance queries: the bounce loop on caller-supplied rays (rtx_radiance*,
 // include/rtx.h; DESIGN.md §4e "Radiance queries").  Included once, by rtx_queries.hip, after the
 // trace kernels.  Nothing here is used by a render kernel: k_persistent, k_wf_*, k_intersect and
-// trace<>() are as they were; the kernels below call the same device functions.
+// trace<>() are as they were; the kernels below call the same device functions.  The slot decode
+// (chunk_slot) and the slot write (slot_write) defined here are the one definition every query
+// kernel that takes a RadianceChunk shares.  The bounce loop stands twice, here and in
+// k_irradiance, token for token: as a function of its own it costs both kernels registers (the
+// parity walk: 48 -> 64 B of scratch, 28 -> 40 spilled VGPRs), so it stays written out.
 //
 // Contract: for ray i and sample k the lane traces the path the wavefront renderer traces from
 // the same depth-0 segment: per segment the closest hit of k_wf_extend (trace<> on
@@ -32,19 +36,43 @@ struct RadianceChunk {
   uint32_t* segs;       // segments per slot
 };
 
+// Slot j of a chunk: the index i of its ray in the caller's arrays and its sample's place k in the
+// chunk (sample s0 + k) ...
+__device__ __forceinline__ void chunk_index(const RadianceChunk& A, uint32_t j, int64_t& i, uint32_t& k) {
+  const uint32_t r = j / A.K;
+  k = j - r * A.K;
+  i = A.ray0 + (int64_t)r;
+}
+// ... and the caller's ray (or surfel), pixel key and sample number: the one decode of every kernel
+// that takes a RadianceChunk of caller-supplied rays
+__device__ __forceinline__ void chunk_slot(const RadianceChunk& A, uint32_t j, rtx_ray& ray, uint32_t& pix,
+                                           uint32_t& smp) {
+  int64_t i;
+  uint32_t k;
+  chunk_index(A, j, i, k);
+  ray = A.rays[i];
+  pix = A.ids ? A.ids[i] : (uint32_t)(A.id_base + (uint64_t)i);
+  smp = (uint32_t)A.s0 + k;
+}
+// Slot j's result: three doubles and a count
+__device__ __forceinline__ void slot_write(double* L, uint32_t* segs, uint32_t j, V3 v, uint32_t n) {
+  double* Lp = L + 3 * (uint64_t)j;
+  Lp[0] = v.x, Lp[1] = v.y, Lp[2] = v.z;
+  segs[j] = n;
+}
+
 // One lane per slot: the whole path, the traversal stack in the lane's LDS column as in
 // k_intersect.  A lane whose path has ended idles until its wave's longest path ends (no refill).
+// (From `P.thr` to the loop's end the text is k_irradiance's too: change both or neither.)
 template <int STACK, bool FAST>
 __global__ __launch_bounds__(kBlock, kTraceWaves) void k_radiance(DScene S, RadianceChunk A) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   uint32_t* stk = lds + threadIdx.x;
   const uint32_t j = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
   if (j >= A.slots) return;
-  const uint32_t r = j / A.K, k = j - r * A.K;
-  const int64_t i = A.ray0 + (int64_t)r;
-  const rtx_ray ray = A.rays[i];
-  const uint32_t pix = A.ids ? A.ids[i] : (uint32_t)(A.id_base + (uint64_t)i);
-  const uint32_t smp = (uint32_t)A.s0 + k;
+  rtx_ray ray;
+  uint32_t pix, smp;
+  chunk_slot(A, j, ray, pix, smp);
   Path P;
   P.o = v3(ray.origin[0], ray.origin[1], ray.origin[2]);
   P.d = v3(ray.direction[0], ray.direction[1], ray.direction[2]);
@@ -62,9 +90,7 @@ __global__ __launch_bounds__(kBlock, kTraceWaves) void k_radiance(DScene S, Radi
     Rng g = make_rng(A.seed, pix, smp, (uint32_t)P.depth + 1u);
     if (!shade(S, A.max_depth, P, h, best >= 0, g, L)) break;
   }
-  double* Lp = A.L + 3 * (uint64_t)j;
-  Lp[0] = L.x, Lp[1] = L.y, Lp[2] = L.z;
-  A.segs[j] = segs;
+  slot_write(A.L, A.segs, j, L, segs);
 }
 
 // One lane per ray of the chunk: the ray's K slot radiances added in sample order (plain f64
