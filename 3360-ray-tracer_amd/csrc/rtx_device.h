@@ -13,6 +13,7 @@
 #include <type_traits>
 
 #include "rtx.h"
+#include "rtx_f4node.h"
 
 // Per-translation-unit choices.  rtx_park.hip, which compiles the PARK instantiations of
 // k_persistent and nothing else, defines RTX_PARK_TU 1 before including this file; every
@@ -266,21 +267,7 @@ struct DImage {
   const uint8_t* texels;
 };
 
-// 4-wide fast node (RTX_PREC_FAST): a binary SAH tree collapsed so every node holds up to four
-// children's outward-rounded f32 boxes (SoA for the four slab tests; build_fast4).  Every leaf
-// slot holds exactly one primitive: child >= 0: node index; child < 0: leaf, ~child = the
-// primitive; counts[]: 1 for a leaf slot (read by no kernel: the lean walk relies on the
-// one-primitive layout); an empty slot is an inverted box (lo = +inf, hi = -inf, child -1) that
-// no ray enters.  128 bytes = two cache lines.
-struct F4Node {
-  float lox[4], hix[4], loy[4], hiy[4], loz[4], hiz[4];  // axis a: lo at 32a, hi at 32a + 16 bytes
-  int32_t child[4];
-  uint32_t counts[2];
-  uint32_t pad_[2];
-};
-static_assert(sizeof(F4Node) == 128, "F4Node must be two 64-byte lines");
-
-typedef F4Node FastNode;
+typedef F4Node FastNode;  // the 4-wide fast node (RTX_PREC_FAST): rtx_f4node.h
 
 struct DScene {
   const rtx_bvh_node* nodes;  // parity layout, reference pre-order
@@ -301,7 +288,7 @@ struct DScene {
   // (0..2); bit 2 (kGlobalSpheres): all of them are plain spheres (trav_globals).  Read the
   // count as n_global & 3.
   int32_t n_global;
-  int32_t global[2];  // their indices into prims (see build_global_prims, rtx_capi.hip)
+  int32_t global[2];  // their indices into prims (see build_global_prims, rtx_scene_plan.cc)
   const double* tri_n;  // per primitive (x, y, z, 0), a triangle's unit normal (nullptr: no triangles)
 };
 
@@ -760,7 +747,7 @@ __device__ __forceinline__ void pin(V3& v) {
 // hit is the same up to exact t ties.  Per node: four slab tests, the hit leaves' primitives
 // (one per leaf slot), then the surviving internal children sorted by entry distance; the
 // nearest is visited next, the others are pushed far-to-near.  The host sizes the stack from
-// the exact worst-case push depth of the collapsed tree (rtx_capi.hip build_fast4).
+// the exact worst-case push depth of the collapsed tree (rtx_scene_plan.cc build_fast4).
 //
 // Slab test, one FMA per plane: t = fma(plane, inv, n) with n = -(o * inv) -/+ delta.
 // With inv = 1/RN(d) to within one ulp (v_rcp_f32), o_f = RN(o), n0 = RN(-o_f * inv), the

@@ -1,6 +1,7 @@
 // rtx_host.h — the host-side internals the C ABI's translation units share (rtx_capi.hip: scenes,
 // films, renders; rtx_queries.hip: the ray-query entry points): error reporting, device and
-// pinned buffers, the scene and film objects behind the opaque handles of include/rtx.h, the
+// pinned buffers that free themselves (DevBuf, HostBuf: a scene's or a film's memory goes with
+// its members, no list names them), the scene and film objects behind the opaque handles of include/rtx.h, the
 // pixel subset of a render, and the one dispatch of a traversal kernel on a scene's walk
 // (with_walk, launch_1d).  Host code only; no kernel is defined here.
 #pragma once
@@ -35,9 +36,17 @@ inline int fail(int code, const std::string& msg) {
                                    std::to_string(__LINE__) + ")");                                  \
   } while (0)
 
+// Device memory that frees itself (grow-only; move-only)
 struct DevBuf {
   void* p = nullptr;
   size_t n = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr, o.n = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) release(), p = o.p, n = o.n, o.p = nullptr, o.n = 0;
+    return *this;
+  }
+  ~DevBuf() { release(); }
   int reserve(size_t bytes) {
     if (bytes <= n) return RTX_OK;
     if (p) (void)hipFree(p);
@@ -58,9 +67,16 @@ struct DevBuf {
   }
 };
 
-struct HostBuf {  // pinned host staging (grow-only)
+struct HostBuf {  // pinned host staging (grow-only; move-only, frees itself)
   void* p = nullptr;
   size_t n = 0;
+  HostBuf() = default;
+  HostBuf(HostBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr, o.n = 0; }
+  HostBuf& operator=(HostBuf&& o) noexcept {
+    if (this != &o) release(), p = o.p, n = o.n, o.p = nullptr, o.n = 0;
+    return *this;
+  }
+  ~HostBuf() { release(); }
   int reserve(size_t bytes) {
     if (bytes <= n) return RTX_OK;
     if (p) (void)hipHostFree(p);
@@ -88,19 +104,22 @@ struct AdaptWs {
   DevBuf segs;                                  // counting renders: each slot's path segments (u16)
   HostBuf total_h;                              // pinned copy of the next phase's slot count
   hipEvent_t ev = nullptr;                      // total_h written
-  void release() {
-    for (DevBuf* b : {&lbuf, &smap, &lst[0], &lst[1], &kl[0], &kl[1], &ol[0], &ol[1], &knext, &pk, &rv, &scan_tmp, &ctr,
-                      &segs})
-      b->release();
-    total_h.release();
+  ~AdaptWs() {
     if (ev) (void)hipEventDestroy(ev);
-    ev = nullptr;
   }
 };
 
 // A film (rtx_film_*): its own pixel state on its scene's device; everything else a render needs
 // (radiance slots, queues, counters, the adaptive workspace) stays the scene's scratch.
-struct rtx_film {
+// Every buffer of a film lives here, so that release() below cannot miss one
+struct FilmBufs {
+  DevBuf sum, mean, m2, samples, conv;  // mean / m2: adaptive films only
+  mutable DevBuf stage;     // save / load: the blob's body on the device
+  // rtx_film_denoise*: the packed guide and albedo of the film's pixels (float4 each), made on
+  // first use; not part of the saved state
+  DevBuf dn_guide, dn_alb;
+};
+struct rtx_film : FilmBufs {
   rtx_scene* sc = nullptr;  // nullptr once the scene was destroyed (the film's memory went with it)
   int device = 0;
   rtx_camera cam{};
@@ -114,17 +133,12 @@ struct rtx_film {
   int32_t estimator = 0;
   int64_t active = -1;
   int64_t epoch = 0;        // the scene's epoch the film was created or last reset at (rtx_film_reset)
-  DevBuf sum, mean, m2, samples, conv;  // mean / m2: adaptive films only
-  mutable DevBuf stage;     // save / load: the blob's body on the device
-  // rtx_film_denoise*: the packed guide and albedo of the film's pixels (float4 each), made on
-  // first use; not part of the saved state
-  DevBuf dn_guide, dn_alb;
   bool aov_ready = false;
   PixelSoA px() const {
     return PixelSoA{sum.as<double>(), mean.as<double>(), m2.as<double>(), samples.as<int32_t>(), conv.as<uint8_t>()};
   }
-  void release() {
-    for (DevBuf* b : {&sum, &mean, &m2, &samples, &conv, &stage, &dn_guide, &dn_alb}) b->release();
+  void release() {  // an empty film: what is left of one that outlives its scene
+    static_cast<FilmBufs&>(*this) = FilmBufs{};
     aov_ready = false;
   }
 };
@@ -211,26 +225,13 @@ struct rtx_scene {
     // films outlive their scene as empty shells: their device memory goes here, and every call
     // on them but rtx_film_destroy fails from now on
     for (rtx_film* f : films) f->release(), f->sc = nullptr;
-    aw.release();
-    fs_ctr.release(), fs_host.release();
     for (auto e : evpool) (void)hipEventDestroy(e);
     for (auto e : band_ev) (void)hipEventDestroy(e);
     if (copy_stream) (void)hipStreamDestroy(copy_stream);
-    (void)hipSetDevice(device);
-    for (DevBuf* b : {&ref_box, &fast_box, &node_order, &f4_order, &upd_stage}) b->release();
-    upd_host.release();
-    for (DevBuf* b : {&nodes, &prims, &mats, &texs, &images, &fnodes, &tri_n, &px_sum, &px_mean, &px_m2, &px_samples,
-                      &px_conv, &lbuf, &queue[0], &queue[1], &counters, &out_rgb, &out_spp, &rays, &hits, &p3_scratch,
-                      &p3_body, &calib_rgb, &patch_q, &aov_f64, &dn_in, &dn_var, &dn_work[0], &dn_work[1], &dn_guide,
-                      &dn_alb, &occ, &rad_L, &rad_segs, &rad_carry, &rad_ids, &rad_out, &rad_oseg,
-                      &emit_prim, &emit_cum})
-      b->release();
-    rad_host.release();
-    for (auto& t : texels) t.release();
-    stage_rgb.release(), stage_spp.release();
     for (auto& e : ev)
       if (e) (void)hipEventDestroy(e);
     if (stream) (void)hipStreamDestroy(stream);
+    // the buffers (DevBuf, HostBuf) and the adaptive workspace free themselves after this
   }
 };
 

@@ -103,9 +103,7 @@ extern "C" int rtx_internal_cos_sin_forms(int device, const double* phi, int64_t
   if (n < 0 || n_draws < 0 || n + n_draws > ((int64_t)1 << 32) || (n > 0 && !phi) || !mismatches)
     return fail(RTX_ERR_INVALID, "bad argument");
   HIPC(hipSetDevice(device));
-  struct Owned : DevBuf {
-    ~Owned() { release(); }
-  } res, in, out;
+  DevBuf res, in, out;
   int rc;
   if ((rc = res.reserve(2 * sizeof(unsigned long long)))) return rc;
   if ((rc = in.reserve((size_t)n * sizeof(double)))) return rc;
@@ -140,9 +138,7 @@ extern "C" int rtx_internal_visit_order(rtx_scene* sc, const double* rays, int64
   if (!sc->fast_ok || sc->n_f4 == 0 || sc->n_f4 >= 65536 || (sc->stack_fast != 32 && sc->stack_fast != 64))
     return fail(RTX_ERR_INVALID, "the scene has no fast tree the speculative walk runs on");
   HIPC(hipSetDevice(sc->device));
-  struct Owned : DevBuf {
-    ~Owned() { release(); }
-  } in, oseq, ot, olen, ofr;
+  DevBuf in, oseq, ot, olen, ofr;
   int rc;
   const size_t un = (size_t)n;
   if ((rc = in.reserve(un * 6 * sizeof(double)))) return rc;

@@ -10,10 +10,7 @@
 #include <stdint.h>
 
 #include "rtx.h"
-
-namespace rtxd {
-struct F4Node;
-}
+#include "rtx_f4node.h"
 
 namespace rtxrefit {
 

@@ -90,6 +90,14 @@ def query_cases(rtx, res):
             put(f"nee_samples depth {d}", rtx.nee_samples(dev, pts, nrm, spp, 99, d, ids=sid, first_sample=s0))
 
 
+def tree_cases(rtx, res):
+    """The trees each stock scene holds on the device after its upload (rtx.scene_trees), as bytes."""
+    for scene in ("three", "final", "mixed", "bunny", "cornell"):
+        dev = rtx.DeviceScene(rtx.HostScene.recipe(scene, 1234), device=0)
+        for k, a in enumerate(rtx.scene_trees(dev)):
+            res[f"q trees {scene} [{k}]"] = np.frombuffer(a.tobytes(), np.uint8)
+
+
 def child(out, what):
     sys.path.insert(0, os.path.join(ROOT, "3360-ray-tracer_amd"))
     import torch  # noqa: F401  (HIP runtime before librtx, as bench.py)
@@ -99,6 +107,7 @@ def child(out, what):
     res = {}
     if what != "renders":
         query_cases(rtx, res)
+        tree_cases(rtx, res)
     for i, (scene, preset, w, spp, depth, mode, prec, adaptive, *sched) in enumerate(CASES if what != "queries" else []):
         dev = rtx.DeviceScene(rtx.HostScene.recipe(scene, 1234), device=0)
         cam = rtx.camera(rtx.camera_config(preset, width=w))
