@@ -15,6 +15,7 @@
 // pass-by-pass order regardless of how lanes, queues or XCDs interleave the work.
 #pragma once
 
+#include "rtx_bounds.h"
 #include "rtx_device.h"
 
 namespace rtxd {
@@ -254,6 +255,49 @@ __device__ __forceinline__ void flush_counters(const RenderArgs& A, const Counte
 // ---------------------------------------------------------------------------------------
 // IntersectBatch
 // ---------------------------------------------------------------------------------------
+// Where the fast walk of a ray query (k_intersect, k_occluded) stands in for the parity walk, and
+// where it does not.  The f32 slab test is conservative: it enters every box the reference's f64
+// Aabb::Hit enters.  The two part in two places, and there the query runs the parity walk in the
+// ray's lane, so it reports what the reference does (the host sizes the lane's stack for either
+// walk: query_walk, rtx_queries.hip):
+//  * fast_query_domain: a component without a usable f32 reciprocal.  Every direction component
+//    must be zero or a normal f32 whose reciprocal is one too (2^-126 <= |d| <= 2^126), every
+//    origin component within 2^126; a NaN fails the comparisons.  visit_slabs' proof assumes this.
+//  * face_plane_hit: a zero direction component on axis a makes Aabb::Hit's plane distances
+//    (plane - o) * inf, so the reference enters a box only if lo < o < hi there (on a face 0 * inf
+//    is NaN and the comparisons reject the box), while the f32 test drops the axis.  Every box
+//    above a primitive contains the primitive's own (rtxb::ref_bounds), so if o lies strictly inside
+//    that one on each zero axis no box above it is rejected this way and the fast walk's hit
+//    stands; otherwise (a tangent sphere, a rect hit on its edge) the parity walk decides.  A
+//    triangle's box is padded by 1e-6 and rebuilt here from the edge form, exact to an ulp: beyond
+//    2^20 the padding is no longer far above that ulp, and the parity walk decides as well.
+__device__ __forceinline__ bool fast_query_domain(V3 o, V3 d) {
+  const double lo = 0x1p-126, hi = 0x1p126;
+  const double ax = fabs(d.x), ay = fabs(d.y), az = fabs(d.z);
+  return (ax == 0.0 || (ax >= lo && ax <= hi)) && (ay == 0.0 || (ay >= lo && ay <= hi)) &&
+         (az == 0.0 || (az >= lo && az <= hi)) && fabs(o.x) <= hi && fabs(o.y) <= hi && fabs(o.z) <= hi;
+}
+__device__ __forceinline__ bool face_plane_hit(const DScene& S, int64_t prim, V3 o, V3 d) {
+  if (d.x != 0.0 && d.y != 0.0 && d.z != 0.0) return false;
+  const rtx_prim* __restrict__ P = S.prims + prim;
+  const int kind = P->kind;
+  double g[9], b[6];
+#pragma unroll
+  for (int i = 0; i < 9; i++) g[i] = P->g[i];
+  const bool tri = kind == RTX_PRIM_TRIANGLE;
+  if (tri) {  // the device table holds A, B - A, C - A
+#pragma unroll
+    for (int a = 0; a < 3; a++) g[3 + a] += g[a], g[6 + a] += g[a];
+  }
+  rtxb::ref_bounds(kind, g, b);
+  bool out = false;
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    const double oa = comp(o, a);
+    if (comp(d, a) == 0.0) out |= !(b[a] < oa && oa < b[3 + a]) || (tri && fabs(oa) > 0x1p20);
+  }
+  return out;
+}
 template <int STACK, bool FAST>
 __global__ __launch_bounds__(kBlock, kTraceWaves) void k_intersect(DScene S, const rtx_ray* __restrict__ rays,
                                                                        int64_t n, rtx_hit* __restrict__ hits,
@@ -266,7 +310,13 @@ __global__ __launch_bounds__(kBlock, kTraceWaves) void k_intersect(DScene S, con
   V3 o{r.origin[0], r.origin[1], r.origin[2]}, d{r.direction[0], r.direction[1], r.direction[2]};
   Counters c{};
   double tb;
-  const int64_t best = trace<STACK, FAST, false>(S, o, d, tmin, tmax, stk, c, tb);
+  int64_t best;
+  if (FAST && !fast_query_domain(o, d)) {
+    best = trace<STACK, false, false>(S, o, d, tmin, tmax, stk, c, tb);
+  } else {
+    best = trace<STACK, FAST, false>(S, o, d, tmin, tmax, stk, c, tb);
+    if (FAST && best >= 0 && face_plane_hit(S, best, o, d)) best = trace<STACK, false, false>(S, o, d, tmin, tmax, stk, c, tb);
+  }
   rtx_hit out;
   out.pad_ = 0;
   if (best >= 0) {

@@ -37,10 +37,15 @@ __device__ __forceinline__ bool occl_prim(const DScene& S, uint32_t i, V3 o, V3 
 
 // The flat list (a scene without nodes), or the fast BVH's single-leaf root: trace_flat's
 // counterpart.
-__device__ __forceinline__ bool occluded_flat(const DScene& S, V3 o, V3 d, double tmin, double tmax) {
+// (who, here and below: where given, it receives the primitive that was accepted)
+__device__ __forceinline__ bool occluded_flat(const DScene& S, V3 o, V3 d, double tmin, double tmax,
+                                              int64_t* who = nullptr) {
   const int64_t n = S.use_bvh ? S.froot_count : S.n_prims;
   for (int64_t i = 0; i < n; i++)
-    if (occl_prim(S, (uint32_t)i, o, d, tmin, tmax)) return true;
+    if (occl_prim(S, (uint32_t)i, o, d, tmin, tmax)) {
+      if (who) *who = i;
+      return true;
+    }
   return false;
 }
 
@@ -78,7 +83,8 @@ __device__ __forceinline__ bool occluded_parity(const DScene& S, V3 o, V3 d, dou
 // The global primitives (kept out of the fast tree), tested first, in the converged start of the
 // walk, as trav_globals does: plain spheres (kGlobalSpheres) from uniform loads of the record
 // with g[4] = radius * radius and sphere_root's one division, else the generic test.
-__device__ __forceinline__ bool occluded_globals(const DScene& S, V3 o, V3 d, double tmin, double tmax) {
+__device__ __forceinline__ bool occluded_globals(const DScene& S, V3 o, V3 d, double tmin, double tmax,
+                                                 int64_t* who = nullptr) {
   bool occ = false;
   if (S.n_global & kGlobalSpheres) {
     typedef uint32_t u4 __attribute__((ext_vector_type(4)));
@@ -95,12 +101,18 @@ __device__ __forceinline__ bool occluded_globals(const DScene& S, V3 o, V3 d, do
       const double cc = len2(oc) - w2.y;
       const double disc = h * h - a * cc;
       double t;
-      if (!(disc < 0) && sphere_root(a, h, sqrt(disc), tmin, tmax, t)) occ = true;
+      if (!(disc < 0) && sphere_root(a, h, sqrt(disc), tmin, tmax, t)) {
+        occ = true;
+        if (who) *who = S.global[i];
+      }
     }
     return occ;
   }
   for (int i = 0; i < S.n_global; i++)
-    if (occl_prim(S, (uint32_t)S.global[i], o, d, tmin, tmax)) occ = true;
+    if (occl_prim(S, (uint32_t)S.global[i], o, d, tmin, tmax)) {
+      occ = true;
+      if (who) *who = S.global[i];
+    }
   return occ;
 }
 
@@ -114,9 +126,9 @@ __device__ __forceinline__ bool occluded_globals(const DScene& S, V3 o, V3 d, do
 // below are unconditional at sp, one slot above the deepest entry at most, as in visit_next.
 template <int STACK>
 __device__ __forceinline__ bool occluded_fast4(const DScene& S, V3 o, V3 d, double tmin, double tmax, uint32_t* stk,
-                                               int stride) {
-  if (!S.use_bvh || S.froot_leaf) return occluded_flat(S, o, d, tmin, tmax);
-  if (occluded_globals(S, o, d, tmin, tmax)) return true;
+                                               int stride, int64_t* who = nullptr) {
+  if (!S.use_bvh || S.froot_leaf) return occluded_flat(S, o, d, tmin, tmax, who);
+  if (occluded_globals(S, o, d, tmin, tmax, who)) return true;
   const FRay4L r = make_fray4l(o, d);
   const char* __restrict__ nbase = (const char*)S.f4nodes;
   const float tmax_x = f32_round_up(tmax) * 1.00001f;  // exit-side clamp with the slack folded in
@@ -129,7 +141,10 @@ __device__ __forceinline__ bool occluded_fast4(const DScene& S, V3 o, V3 d, doub
     while (lmask) {  // the visit's leaf slots
       const uint32_t cur = leaf_prim(cc, __builtin_ctz(lmask));
       lmask &= lmask - 1u;
-      if (occl_prim(S, cur, o, d, tmin, tmax)) return true;
+      if (occl_prim(S, cur, o, d, tmin, tmax)) {
+        if (who) *who = cur;
+        return true;
+      }
     }
     const float tn = fminf(fminf(tt[0], tt[1]), fminf(tt[2], tt[3]));
     if (tn != __builtin_inff()) {
@@ -164,7 +179,19 @@ __global__ __launch_bounds__(kBlock, kTraceWaves) void k_occluded(DScene S, cons
   if (i >= n) return;
   const rtx_ray r = rays[i];
   const V3 o{r.origin[0], r.origin[1], r.origin[2]}, d{r.direction[0], r.direction[1], r.direction[2]};
-  out[i] = occluded<STACK, FAST>(S, o, d, tmin, tmax, stk) ? (uint8_t)1 : (uint8_t)0;
+  // (the parity walk where the two box tests part, as in k_intersect: fast_query_domain, and an
+  // accepted primitive that a face-plane ray touches, face_plane_hit)
+  bool occ;
+  if (FAST && !fast_query_domain(o, d)) {
+    occ = occluded<STACK, false>(S, o, d, tmin, tmax, stk);
+  } else if (FAST) {
+    int64_t who = -1;
+    occ = occluded_fast4<STACK>(S, o, d, tmin, tmax, stk, kBlock, &who);
+    if (occ && face_plane_hit(S, who, o, d)) occ = occluded<STACK, false>(S, o, d, tmin, tmax, stk);
+  } else {
+    occ = occluded<STACK, false>(S, o, d, tmin, tmax, stk);
+  }
+  out[i] = occ ? (uint8_t)1 : (uint8_t)0;
 }
 
 // ---------------------------------------------------------------------------------------

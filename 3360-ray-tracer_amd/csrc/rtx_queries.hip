@@ -496,6 +496,17 @@ int film_sampled_render(rtx_film* f, int32_t budget, rtx_stats* stats) {
   return RTX_OK;
 }
 
+// The walk of rtx_intersect* / rtx_occluded*.  The fast walk clamps a box's entry distance at 0
+// (visit_slabs), so it culls geometry behind the origin that a negative tmin asks for, and the f64
+// slab test rejects every box on an empty range: such a query runs the parity walk, whatever
+// precision it names (include/rtx.h).  A fast query's kernel sends single rays to the parity walk
+// too (fast_query_domain, rtx_kernels.h), so its lanes get the deeper of the two stacks.
+template <class F>
+static int query_walk(const rtx_scene* sc, int32_t precision, double tmin, double tmax, F&& f) {
+  const bool fast = precision == RTX_PREC_FAST && sc->fast_ok && tmin >= 0.0 && tmin < tmax;
+  return with_walk(fast ? std::max(sc->stack_fast, sc->stack_parity) : sc->stack_parity, fast, f);
+}
+
 extern "C" {
 
 int rtx_intersect_device(rtx_scene* sc, const rtx_ray* d_rays, size_t n, rtx_hit* d_hits, double tmin, double tmax,
@@ -505,7 +516,7 @@ int rtx_intersect_device(rtx_scene* sc, const rtx_ray* d_rays, size_t n, rtx_hit
   if (!d_rays || !d_hits) return fail(RTX_ERR_INVALID, "NULL buffer");
   HIPC(hipSetDevice(sc->device));
   hipStream_t s = stream ? (hipStream_t)stream : sc->stream;
-  return with_walk(sc, precision, [&](auto w) {
+  return query_walk(sc, precision, tmin, tmax, [&](auto w) {
     return launch_1d(k_intersect<w.stack, w.fast>, (int64_t)n, stack_lds_bytes(w.stack), s, sc->S, d_rays, (int64_t)n,
                      d_hits, tmin, tmax);
   });
@@ -537,7 +548,7 @@ int rtx_occluded_device(rtx_scene* sc, const rtx_ray* d_rays, size_t n, uint8_t*
   if (!d_rays || !d_out) return fail(RTX_ERR_INVALID, "NULL buffer");
   HIPC(hipSetDevice(sc->device));
   hipStream_t s = stream ? (hipStream_t)stream : sc->stream;
-  return with_walk(sc, precision, [&](auto w) {
+  return query_walk(sc, precision, tmin, tmax, [&](auto w) {
     return launch_1d(k_occluded<w.stack, w.fast>, (int64_t)n, stack_lds_bytes(w.stack), s, sc->S, d_rays, (int64_t)n,
                      d_out, tmin, tmax);
   });

@@ -299,7 +299,15 @@ int rtx_scene_epoch(const rtx_scene* scene, int64_t* epoch);
  * must be pre-order (children after their parent) with leaf ranges inside n. */
 int rtx_bvh_refit_host(rtx_bvh_node* nodes, int64_t n_nodes, const double* bounds, int64_t n);
 
-/* Batch closest hit on [tmin, tmax); host buffers (PCIe round trip included). */
+/* Batch closest hit on [tmin, tmax); host buffers (PCIe round trip included).  tmin may be
+ * negative (hits behind the origin are then reported, as the reference's Interval(tmin, tmax)
+ * does); the fast walk clamps box entry distances at 0, so a query with tmin < 0 (or an empty
+ * range, tmin >= tmax) runs the parity walk whatever precision it names.  In a fast query a single
+ * ray takes the parity walk where the reference's f64 box test and the conservative f32 one part: a
+ * direction component that is NaN or nonzero outside 2^-126 .. 2^126 in magnitude, an origin
+ * component beyond 2^126 or NaN, or an axis-parallel ray that touches the primitive it hits in (or
+ * outside) a face plane of that primitive's box, where the reference rejects the box (0 * inf).  The
+ * query then reports what the reference does.  The same holds for rtx_occluded*. */
 int rtx_intersect(rtx_scene* scene, const rtx_ray* rays, size_t n, rtx_hit* hits, double tmin, double tmax,
                   int32_t precision);
 /* Same on device-resident buffers; stream is a hipStream_t (NULL = the scene's stream). */

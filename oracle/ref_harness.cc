@@ -708,7 +708,7 @@ void usage() {
                "ref_harness recipe <name> <out.rtxs>\n"
                "ref_harness rng <seed> <n>\n"
                "ref_harness bvh <scene.rtxs> <model_dir> <out_prefix>\n"
-               "ref_harness hits <scene.rtxs> <model_dir> <rays.f64> <tmin> <out.f64>\n"
+               "ref_harness hits <scene.rtxs> <model_dir> <rays.f64> <tmin> [<tmax>] <out.f64>\n"
                "ref_harness aabb <boxes_rays.f64> <out.i32>\n"
                "ref_harness material <cases.f64> <out.f64>\n"
                "ref_harness scatter <cases.f64> <out.f64>\n"
@@ -769,10 +769,16 @@ int main(int argc, char** argv) {
     write_bin(out + ".links.u32", links);
     std::vector<int32_t> pi(S->bvh->prim_indices().begin(), S->bvh->prim_indices().end());
     write_bin(out + ".prims.i32", pi);
-  } else if (cmd == "hits" && argc == 7) {
+  } else if (cmd == "hits" && (argc == 7 || argc == 8)) {
+    // optional <tmax> (as strtod reads it: hex floats, inf): the closest hit on Interval(tmin, tmax)
+    // with tmin taken as given, negative values included; without it tmax is infinity and a
+    // negative tmin selects the IntersectBatch seam, as before
     auto S = load_scene(argv[2], argv[3]);
     auto rays = read_bin<double>(argv[4]);
-    double tmin = std::atof(argv[5]);
+    const bool ranged = argc == 8;
+    double tmin = ranged ? std::strtod(argv[5], nullptr) : std::atof(argv[5]);
+    const double tmax = ranged ? std::strtod(argv[6], nullptr) : core::kInfinity;
+    const char* out_path = argv[argc - 1];
     size_t n = rays.size() / 6;
     // 12 doubles per ray: hit t p[3] n[3] u v front_face mat
     std::vector<double> out(12 * n, 0.0);
@@ -781,7 +787,7 @@ int main(int argc, char** argv) {
                   Vec3(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]));
       geom::HitRecord rec{};
       bool ok;
-      if (tmin < 0) {  // IntersectBatch seam: fixed [0.001f, inf) (cpu_ray_integrator.h:21-29)
+      if (!ranged && tmin < 0) {  // IntersectBatch seam: fixed [0.001f, inf) (cpu_ray_integrator.h:21-29)
         std::vector<core::Ray> one{r};
         std::vector<geom::HitRecord> h;
         integrator::CPURayIntegrator integ(&S->world);
@@ -789,7 +795,7 @@ int main(int argc, char** argv) {
         rec = h[0];
         ok = rec.hit;
       } else {
-        ok = S->world.Hit(r, core::Interval(tmin, core::kInfinity), rec);
+        ok = S->world.Hit(r, core::Interval(tmin, tmax), rec);
       }
       double* o = &out[12 * i];
       o[0] = ok;
@@ -802,7 +808,7 @@ int main(int argc, char** argv) {
         o[11] = S->mat_id[rec.mat.get()];
       }
     }
-    write_bin(argv[6], out);
+    write_bin(out_path, out);
   } else if (cmd == "aabb" && argc == 4) {
     // per case: box(6: xmin xmax ymin ymax zmin zmax) ray(6) tmin tmax = 14 doubles
     auto c = read_bin<double>(argv[2]);

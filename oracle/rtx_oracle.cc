@@ -1300,6 +1300,32 @@ int orc_intersect(void* sp, const double* rays, long long n, double tmin, double
   }
   return 0;
 }
+// The range form: the closest hit on Interval(tmin, tmax), both taken as given (a negative tmin
+// is a negative tmin, not the seam).  Same record layout.  -1 (orc_last_error) on a NULL scene, a
+// negative n, a NULL buffer with n > 0, or a NaN bound.
+int orc_intersect_range(void* sp, const double* rays, long long n, double tmin, double tmax, double* out,
+                        int threads) {
+  Scene* s = (Scene*)sp;
+  if (!s) return g_err = "orc_intersect_range: scene is NULL", -1;
+  if (n < 0) return g_err = "orc_intersect_range: negative ray count", -1;
+  if (n > 0 && (!rays || !out)) return g_err = "orc_intersect_range: NULL buffer", -1;
+  if (tmin != tmin || tmax != tmax) return g_err = "orc_intersect_range: NaN bound", -1;
+#pragma omp parallel for num_threads(threads > 0 ? threads : 1)
+  for (long long i = 0; i < n; i++) {
+    V3 o{rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]}, d{rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]};
+    Hit rec;
+    bool ok = s->hit(o, d, tmin, tmax, rec);
+    double* q = out + 12 * i;
+    std::memset(q, 0, 12 * sizeof(double));
+    q[0] = ok;
+    if (ok) {
+      q[1] = rec.t, q[2] = rec.p.x, q[3] = rec.p.y, q[4] = rec.p.z;
+      q[5] = rec.normal.x, q[6] = rec.normal.y, q[7] = rec.normal.z;
+      q[8] = rec.u, q[9] = rec.v, q[10] = rec.front_face, q[11] = rec.mat;
+    }
+  }
+  return 0;
+}
 // Every primitive whose own closest hit on the ray (hit_prim on (tmin, inf): the near root
 // first, as Scene::Hit would report it) lies at exactly distance t: up to `cap` records of
 // 12 doubles (the orc_intersect layout), brute force over the whole primitive list.  Returns

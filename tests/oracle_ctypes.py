@@ -47,6 +47,8 @@ def lib():
         L.orc_scene_counts.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 4
         L.orc_scene_bvh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_intersect.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_double, C.c_void_p, C.c_int]
+        L.orc_intersect_range.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_double, C.c_double, C.c_void_p,
+                                          C.c_int]
         L.orc_aabb.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p]
         L.orc_tied_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_int]
         L.orc_material.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int]
@@ -125,6 +127,15 @@ class Scene:
         rays = np.ascontiguousarray(rays, dtype=np.float64)
         out = np.zeros((len(rays), 12))
         lib().orc_intersect(self.h, _ptr(rays), len(rays), tmin, _ptr(out), threads)
+        return out
+
+    def intersect_range(self, rays, tmin, tmax, threads=1):
+        """The closest hit on Interval(tmin, tmax), both as given (orc_intersect_range): a
+        negative tmin is a negative tmin, not the seam."""
+        rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+        out = np.zeros((len(rays), 12))
+        if lib().orc_intersect_range(self.h, _ptr(rays), len(rays), tmin, tmax, _ptr(out), threads) != 0:
+            raise RuntimeError(lib().orc_last_error().decode())
         return out
 
     def tied_hits(self, ray, t, tmin=-1.0, cap=16):
