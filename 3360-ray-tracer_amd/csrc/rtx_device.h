@@ -108,6 +108,10 @@ constexpr uint32_t kRngStreamDirect = 0xA2000000u;
 // kRngStreamNee + d, d < max_depth <= 0x00FFFFFF (the entry points' cap), so the streams fill
 // [0xA3000000, 0xA3FFFFFF]: above every segment's stream and apart from the three values above.
 constexpr uint32_t kRngStreamNee = 0xA3000000u;
+// The light probes' sample directions (rtx_probe.h): 0xA4000000, the first value free after the
+// NEE block, written as that block's end so that it moves with it.
+constexpr uint32_t kRngStreamProbe = kRngStreamNee + 0x01000000u;
+static_assert(kRngStreamProbe == 0xA4000000u, "include/rtx.h documents the probes' stream as 0xA4000000");
 __device__ __forceinline__ void philox_block(uint32_t blk, uint32_t sample, uint32_t pixel, uint32_t stream,
                                              uint32_t k0, uint32_t k1, double& u0, double& u1) {
   uint32_t c0 = blk, c1 = sample, c2 = pixel, c3 = stream;

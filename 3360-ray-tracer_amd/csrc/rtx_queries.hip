@@ -3,7 +3,7 @@
 // (rtx_aov*), radiance, irradiance and direct lighting on caller-supplied rays and surfels
 // (rtx_radiance*, rtx_irradiance*, rtx_direct*, rtx_scene_emitters), the light-sampling estimator
 // on rays and on the camera's own frame (rtx_radiance_nee*, rtx_render_nee*) and its power-heuristic
-// form (rtx_radiance_mis*, rtx_render_mis*), with their test hooks, and the render of a sampled film
+// form (rtx_radiance_mis*, rtx_render_mis*), light probes (rtx_probe_sh*), with their test hooks, and the render of a sampled film
 // (film_sampled_render: the frames of those two estimators kept as a film, rtx_film_sampled.h).
 // Scenes, films and the frame renderer are rtx_capi.hip's; the two share rtx_host.h.  Every query
 // picks its walk with with_walk (fast only with a fast tree, the scene's stack size).
@@ -16,6 +16,7 @@
 #include "rtx_irradiance.h"
 #include "rtx_direct.h"
 #include "rtx_nee.h"
+#include "rtx_probe.h"
 #include "rtx_film_sampled.h"
 #include "rtx_scan.h"
 #include "rtx_shade_steps.h"
@@ -347,6 +348,108 @@ int path_trace_hook(rtx_scene* sc, const rtx_ray* rays, const uint32_t* ids, siz
   HIPC(hipMemcpyAsync(flags, d_flags, b_flags, hipMemcpyDeviceToHost, s));
   HIPC(hipMemcpyAsync(counts, d_counts, b_counts, hipMemcpyDeviceToHost, s));
   HIPC(hipStreamSynchronize(s));
+  return RTX_OK;
+}
+// ---- light probes (rtx_probe.h) ----
+// the checks rtx_probe_sh*, and up to the estimator rtx_internal_probe_rays, share, in the documented order
+int probe_check(const rtx_scene* sc, const rtx_radiance_params* prm, const void* points, const void* out,
+                int32_t estimator) {
+  int rc;
+  if ((rc = radiance_check(sc, prm, points, out))) return rc;
+  if (estimator != 0 && estimator != RTX_ESTIMATOR_NEE && estimator != RTX_ESTIMATOR_MIS)
+    return fail(RTX_ERR_INVALID, "probe: bad estimator");
+  if (estimator != 0) return nee_depth_check(prm->max_depth, estimator == RTX_ESTIMATOR_MIS);
+  return RTX_OK;
+}
+// n > 0 probes on device buffers, in radiance_on's chunks (whole probes per chunk, or, when one
+// probe's samples exceed the cap, one probe at a time in runs of `cap` samples whose 27 partial
+// sums and two counts k_probe_sum carries): k_probe into the slot scratch, then k_probe_sum.
+int probe_on(rtx_scene* sc, const double* d_points, const uint32_t* d_ids, uint64_t id_base, int64_t n,
+             const rtx_radiance_params* prm, int32_t estimator, double* d_sh, uint32_t* d_segs, uint32_t* d_back,
+             hipStream_t s) {
+  const int64_t cap = slot_cap();
+  const int64_t spp = prm->spp;
+  const int64_t probes_per = std::max<int64_t>(1, cap / spp);     // probes per chunk
+  const int64_t k_per = std::min<int64_t>(spp, cap);              // samples of a probe per chunk
+  const int64_t most = std::min<int64_t>(n, probes_per) * k_per;  // slots of the largest chunk (<= cap)
+  int rc;
+  if ((rc = sc->rad_L.reserve((size_t)most * 3 * sizeof(double)))) return rc;
+  if ((rc = sc->rad_segs.reserve((size_t)most * sizeof(uint32_t)))) return rc;
+  if (k_per < spp) {  // (one probe per chunk)
+    if ((rc = sc->rad_carry.reserve(kProbeCarry * sizeof(double)))) return rc;
+  }
+  double* const carry = k_per < spp ? sc->rad_carry.as<double>() : nullptr;
+  const EmitterTable E = emitter_table(sc);
+  return with_walk(sc, prm->precision, [&](auto w) {
+    using W = decltype(w);
+    constexpr size_t lds = stack_lds_bytes(W::stack);
+    for (int64_t r0 = 0; r0 < n; r0 += probes_per) {
+      const int64_t nr = std::min<int64_t>(probes_per, n - r0);
+      for (int64_t k0 = 0; k0 < spp; k0 += k_per) {
+        const int64_t K = std::min<int64_t>(k_per, spp - k0);
+        RadianceChunk A;
+        A.rays = nullptr, A.ids = d_ids, A.ray0 = r0, A.id_base = id_base;  // (the points travel beside the chunk)
+        A.slots = (uint32_t)(nr * K), A.K = (uint32_t)K;
+        A.s0 = (int32_t)(prm->first_sample + k0), A.max_depth = prm->max_depth, A.seed = prm->seed;
+        A.L = sc->rad_L.as<double>(), A.segs = sc->rad_segs.as<uint32_t>();
+        if (estimator == 0) rc = launch_1d(k_probe<W::stack, W::fast, 0>, A.slots, lds, s, sc->S, E, A, d_points);
+        else if (estimator == RTX_ESTIMATOR_NEE)
+          rc = launch_1d(k_probe<W::stack, W::fast, RTX_ESTIMATOR_NEE>, A.slots, lds, s, sc->S, E, A, d_points);
+        else rc = launch_1d(k_probe<W::stack, W::fast, RTX_ESTIMATOR_MIS>, A.slots, lds, s, sc->S, E, A, d_points);
+        if (rc) return rc;
+        if ((rc = launch_1d(k_probe_sum, nr, 0, s, A, d_points, nr, k0 == 0 ? 1 : 0, k0 + K == spp ? 1 : 0, prm->spp,
+                            carry, d_sh + 3 * RTX_SH_COEFFS * r0, d_segs ? d_segs + r0 : nullptr,
+                            d_back ? d_back + r0 : nullptr)))
+          return rc;
+      }
+    }
+    return (int)RTX_OK;
+  });
+}
+// The host entry point works in batches of kProbeHostBatch probes, staged through pinned memory as
+// radiance_host stages its rays (the points through `rays`, the coefficients through rad_out, the
+// two counts through rad_oseg).
+constexpr size_t kProbeHostBatch = (size_t)1 << 18;
+int probe_host(rtx_scene* sc, const double* points, const uint32_t* ids, size_t n, const rtx_radiance_params* prm,
+               int32_t estimator, double* out_sh, uint32_t* out_segments, uint32_t* out_backfaces) {
+  int rc;
+  if ((rc = probe_check(sc, prm, points, out_sh, estimator))) return rc;
+  if (n == 0) return RTX_OK;
+  HIPC(hipSetDevice(sc->device));
+  constexpr size_t kSh = 3 * RTX_SH_COEFFS;
+  const size_t m = std::min(n, kProbeHostBatch);
+  // pinned: points | coefficients | ids | segments | back-faces (8-byte items first)
+  const size_t off_sh = m * 3 * sizeof(double), off_ids = off_sh + m * kSh * sizeof(double),
+               off_seg = off_ids + m * sizeof(uint32_t), off_back = off_seg + m * sizeof(uint32_t);
+  if ((rc = sc->rad_host.reserve(off_back + m * sizeof(uint32_t)))) return rc;
+  if ((rc = sc->rays.reserve(m * 3 * sizeof(double)))) return rc;
+  if ((rc = sc->rad_out.reserve(m * kSh * sizeof(double)))) return rc;
+  if ((rc = sc->rad_oseg.reserve(2 * m * sizeof(uint32_t)))) return rc;
+  if (ids && (rc = sc->rad_ids.reserve(m * sizeof(uint32_t)))) return rc;
+  char* const pin = (char*)sc->rad_host.p;
+  uint32_t* const d_seg = sc->rad_oseg.as<uint32_t>();
+  uint32_t* const d_back = d_seg + m;
+  for (size_t b0 = 0; b0 < n; b0 += m) {
+    const size_t nb = std::min(m, n - b0);
+    std::memcpy(pin, points + 3 * b0, nb * 3 * sizeof(double));
+    HIPC(hipMemcpyAsync(sc->rays.p, pin, nb * 3 * sizeof(double), hipMemcpyHostToDevice, sc->stream));
+    if (ids) {
+      std::memcpy(pin + off_ids, ids + b0, nb * sizeof(uint32_t));
+      HIPC(hipMemcpyAsync(sc->rad_ids.p, pin + off_ids, nb * sizeof(uint32_t), hipMemcpyHostToDevice, sc->stream));
+    }
+    if ((rc = probe_on(sc, sc->rays.as<double>(), ids ? sc->rad_ids.as<uint32_t>() : nullptr, (uint64_t)b0, (int64_t)nb,
+                       prm, estimator, sc->rad_out.as<double>(), d_seg, d_back, sc->stream)))
+      return rc;
+    HIPC(hipMemcpyAsync(pin + off_sh, sc->rad_out.p, nb * kSh * sizeof(double), hipMemcpyDeviceToHost, sc->stream));
+    if (out_segments)
+      HIPC(hipMemcpyAsync(pin + off_seg, d_seg, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, sc->stream));
+    if (out_backfaces)
+      HIPC(hipMemcpyAsync(pin + off_back, d_back, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, sc->stream));
+    HIPC(hipStreamSynchronize(sc->stream));
+    std::memcpy(out_sh + kSh * b0, pin + off_sh, nb * kSh * sizeof(double));
+    if (out_segments) std::memcpy(out_segments + b0, pin + off_seg, nb * sizeof(uint32_t));
+    if (out_backfaces) std::memcpy(out_backfaces + b0, pin + off_back, nb * sizeof(uint32_t));
+  }
   return RTX_OK;
 }
 // ---- sampled films (rtx_film_sampled.h) ----
@@ -783,6 +886,50 @@ int rtx_render_mis_device(rtx_scene* sc, const rtx_camera* cam, const rtx_render
 int rtx_render_mis(rtx_scene* sc, const rtx_camera* cam, const rtx_render_params* prm, double* out_rgb,
                    uint32_t* out_segments) {
   return render_nee_host(sc, cam, prm, out_rgb, out_segments, kSlotMis);
+}
+
+// ---- light probes (rtx_probe.h): rtx_radiance's checks, then the estimator's; its chunks and staging ----
+int rtx_probe_sh_device(rtx_scene* sc, const double* d_points, const uint32_t* d_ids, size_t n,
+                        const rtx_radiance_params* prm, int32_t estimator, double* d_out_sh, uint32_t* d_out_segments,
+                        uint32_t* d_out_backfaces, void* stream) {
+  int rc;
+  if ((rc = probe_check(sc, prm, d_points, d_out_sh, estimator))) return rc;
+  if (n == 0) return RTX_OK;
+  HIPC(hipSetDevice(sc->device));
+  return probe_on(sc, d_points, d_ids, 0, (int64_t)n, prm, estimator, d_out_sh, d_out_segments, d_out_backfaces,
+                  stream ? (hipStream_t)stream : sc->stream);
+}
+int rtx_probe_sh(rtx_scene* sc, const double* points, const uint32_t* ids, size_t n, const rtx_radiance_params* prm,
+                 int32_t estimator, double* out_sh, uint32_t* out_segments, uint32_t* out_backfaces) {
+  return probe_host(sc, points, ids, n, prm, estimator, out_sh, out_segments, out_backfaces);
+}
+
+// Test hook (not in rtx.h): the depth-0 segments rtx_probe_sh traces for the same arguments (seed,
+// first_sample and spp of prm are read; the rest is checked as rtx_radiance's), n x spp x 6
+// doubles (origin, direction), probe major, made by the device function k_probe and k_probe_sum
+// call (probe_ray, rtx_probe.h); all zero for a probe with a non-finite coordinate.  Host buffers.
+int rtx_internal_probe_rays(rtx_scene* sc, const double* points, const uint32_t* ids, size_t n,
+                            const rtx_radiance_params* prm, double* out) {
+  int rc;
+  if ((rc = radiance_check(sc, prm, points, out))) return rc;
+  if (n == 0) return RTX_OK;
+  if (n > (size_t)kRadianceSlotsMax || (int64_t)n * prm->spp > kRadianceSlotsMax)
+    return fail(RTX_ERR_INVALID, "probe rays: too many rays for one call");
+  HIPC(hipSetDevice(sc->device));
+  const uint32_t nslots = (uint32_t)(n * (size_t)prm->spp);
+  const size_t bytes = (size_t)nslots * 6 * sizeof(double);
+  if ((rc = sc->rays.reserve(n * 3 * sizeof(double)))) return rc;
+  if ((rc = sc->rad_L.reserve(bytes))) return rc;
+  if (ids && (rc = sc->rad_ids.reserve(n * sizeof(uint32_t)))) return rc;
+  HIPC(hipMemcpyAsync(sc->rays.p, points, n * 3 * sizeof(double), hipMemcpyHostToDevice, sc->stream));
+  if (ids) HIPC(hipMemcpyAsync(sc->rad_ids.p, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, sc->stream));
+  if ((rc = launch_1d(k_probe_rays, nslots, 0, sc->stream, (const double*)sc->rays.as<double>(),
+                      (const uint32_t*)(ids ? sc->rad_ids.as<uint32_t>() : nullptr), nslots, (uint32_t)prm->spp,
+                      prm->seed, prm->first_sample, sc->rad_L.as<double>())))
+    return rc;
+  HIPC(hipMemcpyAsync(out, sc->rad_L.p, bytes, hipMemcpyDeviceToHost, sc->stream));
+  HIPC(hipStreamSynchronize(sc->stream));
+  return RTX_OK;
 }
 
 // Test hook (not in rtx.h): rtx_internal_direct_samples on stream kRngStreamNee + depth, the

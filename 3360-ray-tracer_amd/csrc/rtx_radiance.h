@@ -3,8 +3,8 @@
 // trace kernels.  Nothing here is used by a render kernel: k_persistent, k_wf_*, k_intersect and
 // trace<>() are as they were; the kernels below call the same device functions.  The slot decode
 // (chunk_slot) and the slot write (slot_write) defined here are the one definition every query
-// kernel that takes a RadianceChunk shares.  The bounce loop stands twice, here and in
-// k_irradiance, token for token: as a function of its own it costs both kernels registers (the
+// kernel that takes a RadianceChunk shares.  The bounce loop stands three times, here, in
+// k_irradiance and in k_probe (rtx_probe.h), token for token: as a function of its own it costs the kernels registers (the
 // parity walk: 48 -> 64 B of scratch, 28 -> 40 spilled VGPRs), so it stays written out.
 //
 // Contract: for ray i and sample k the lane traces the path the wavefront renderer traces from
@@ -63,7 +63,8 @@ __device__ __forceinline__ void slot_write(double* L, uint32_t* segs, uint32_t j
 
 // One lane per slot: the whole path, the traversal stack in the lane's LDS column as in
 // k_intersect.  A lane whose path has ended idles until its wave's longest path ends (no refill).
-// (From `P.thr` to the loop's end the text is k_irradiance's too: change both or neither.)
+// (From `P.thr` to the loop's end the text is k_irradiance's too, and k_probe<.., 0>'s in
+// rtx_probe.h but for its back-face line: change all or none.)
 template <int STACK, bool FAST>
 __global__ __launch_bounds__(kBlock, kTraceWaves) void k_radiance(DScene S, RadianceChunk A) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];

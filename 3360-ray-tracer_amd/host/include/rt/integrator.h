@@ -68,6 +68,16 @@ class GpuRayIntegrator : public RayIntegrator {
                    std::vector<core::Vec3>& out, int samples, uint64_t seed,
                    const std::vector<uint32_t>* ids = nullptr, int first_sample = 0,
                    std::vector<uint32_t>* visible = nullptr) const;
+  // Light probes: sh[27 * i + 3 * j + c] = coefficient j, channel c of the radiance arriving at
+  // points[i] over the whole sphere, projected onto the real SH basis to band 2, from `samples`
+  // paths per point in uniform directions (rtx_probe_sh: keyed by (seed, ids ? ids[i] : i,
+  // first_sample + k); estimator 0, RTX_ESTIMATOR_NEE or RTX_ESTIMATOR_MIS).  A non-finite point
+  // gives zeros.  segments / backfaces, if given: per point the segments traced and the samples
+  // whose first segment hit a primitive from inside.  rtx_sh_eval evaluates a probe's 27 doubles.
+  // Not part of the reference's RayIntegrator interface.
+  void ProbeBatch(const std::vector<core::Point3>& points, std::vector<double>& sh, int samples, int max_depth,
+                  uint64_t seed, int estimator = 0, const std::vector<uint32_t>* ids = nullptr, int first_sample = 0,
+                  std::vector<uint32_t>* segments = nullptr, std::vector<uint32_t>* backfaces = nullptr) const;
   rtx_scene* device_scene() const { return dev_; }
   // Replace primitives [first, first + prims.size()) of the device copy, in its own order (leaf
   // order for a BVH world), and refit its trees in place (rtx_scene_update_prims): kinds stay,

@@ -183,3 +183,37 @@ int rtx_image_load(const char* path, int32_t linear8, int32_t* width, int32_t* h
   }
   return RTX_OK;
 }
+
+// A probe's SH coefficients (rtx_probe_sh's layout) at n directions: the reconstruction, or the
+// cosine-convolved value over pi (include/rtx.h).  The basis in rtx.h's order and operations, as
+// the device's sh_basis (csrc/rtx_probe.h) forms it; this unit is built with -ffp-contract=off.
+int rtx_sh_eval(const double* sh, const double* dirs, size_t n, int32_t cosine, double* out_rgb) {
+  if (!sh || ((!dirs || !out_rgb) && n > 0)) return host_fail(RTX_ERR_INVALID, "NULL buffer");
+  if (cosine != 0 && cosine != 1) return host_fail(RTX_ERR_INVALID, "sh eval: cosine must be 0 or 1");
+  for (size_t i = 0; i < n; i++) {
+    const double x = dirs[3 * i], y = dirs[3 * i + 1], z = dirs[3 * i + 2];
+    double Y[RTX_SH_COEFFS];
+    Y[0] = RTX_SH_K0;
+    Y[1] = RTX_SH_K1 * y;
+    Y[2] = RTX_SH_K1 * z;
+    Y[3] = RTX_SH_K1 * x;
+    Y[4] = RTX_SH_K4 * (x * y);
+    Y[5] = RTX_SH_K4 * (y * z);
+    Y[6] = RTX_SH_K6 * (3.0 * (z * z) - 1.0);
+    Y[7] = RTX_SH_K4 * (x * z);
+    Y[8] = RTX_SH_K8 * (x * x - y * y);
+    for (int c = 0; c < 3; c++) {
+      const double* s = sh + c;  // coefficient j of this channel: s[3 * j]
+      if (cosine) {
+        const double b1 = (s[3] * Y[1] + s[6] * Y[2]) + s[9] * Y[3];
+        const double b2 = (((s[12] * Y[4] + s[15] * Y[5]) + s[18] * Y[6]) + s[21] * Y[7]) + s[24] * Y[8];
+        out_rgb[3 * i + c] = (s[0] * Y[0] + (2.0 / 3.0) * b1) + 0.25 * b2;
+      } else {
+        double v = s[0] * Y[0];
+        for (int j = 1; j < RTX_SH_COEFFS; j++) v = v + s[3 * j] * Y[j];
+        out_rgb[3 * i + c] = v;
+      }
+    }
+  }
+  return RTX_OK;
+}

@@ -88,6 +88,26 @@ void GpuRayIntegrator::IrradianceBatch(const std::vector<core::Point3>& points, 
   for (size_t i = 0; i < points.size(); i++) out[i] = core::Vec3(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]);
 }
 
+// The radiance about each point as 9 x 3 SH coefficients (rtx_probe_sh).
+void GpuRayIntegrator::ProbeBatch(const std::vector<core::Point3>& points, std::vector<double>& sh, int samples,
+                                  int max_depth, uint64_t seed, int estimator, const std::vector<uint32_t>* ids,
+                                  int first_sample, std::vector<uint32_t>* segments,
+                                  std::vector<uint32_t>* backfaces) const {
+  sh.assign(3 * RTX_SH_COEFFS * points.size(), 0.0);
+  if (segments) segments->resize(points.size());
+  if (backfaces) backfaces->resize(points.size());
+  if (points.empty()) return;
+  if (ids && ids->size() != points.size()) throw std::invalid_argument("ProbeBatch: one id per point");
+  std::vector<double> p3(3 * points.size());
+  for (size_t i = 0; i < points.size(); i++)
+    for (int k = 0; k < 3; k++) p3[3 * i + k] = points[i][k];
+  rtx_radiance_params p{};
+  p.spp = samples, p.max_depth = max_depth, p.first_sample = first_sample, p.precision = precision_, p.seed = seed;
+  check(rtx_probe_sh(dev_, p3.data(), ids ? ids->data() : nullptr, points.size(), &p, estimator, sh.data(),
+                     segments ? segments->data() : nullptr, backfaces ? backfaces->data() : nullptr),
+        "rtx_probe_sh");
+}
+
 // The light reaching each point straight from the scene's emitters (rtx_direct).
 void GpuRayIntegrator::DirectBatch(const std::vector<core::Point3>& points, const std::vector<core::Vec3>& normals,
                                    std::vector<core::Vec3>& out, int samples, uint64_t seed,

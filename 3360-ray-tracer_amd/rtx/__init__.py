@@ -148,7 +148,7 @@ EXPORTS = ["rtx_abi_version", "rtx_last_error", "rtx_device_count", "rtx_scene_c
            "rtx_irradiance", "rtx_irradiance_device", "rtx_direct", "rtx_direct_device", "rtx_scene_emitters",
            "rtx_radiance_nee", "rtx_radiance_nee_device", "rtx_render_nee", "rtx_render_nee_device",
            "rtx_radiance_mis", "rtx_radiance_mis_device", "rtx_render_mis", "rtx_render_mis_device",
-           "rtx_film_create_sampled"]
+           "rtx_film_create_sampled", "rtx_probe_sh", "rtx_probe_sh_device", "rtx_sh_eval"]
 
 _lib = None
 
@@ -236,6 +236,9 @@ def lib():
             "rtx_radiance_mis_device": ([vp, vp, vp, sz, C.POINTER(RadianceParams), vp, vp, vp], C.c_int),
             "rtx_render_mis": ([vp, C.POINTER(Camera), C.POINTER(RenderParams), vp, vp], C.c_int),
             "rtx_render_mis_device": ([vp, C.POINTER(Camera), C.POINTER(RenderParams), vp, vp, vp], C.c_int),
+            "rtx_probe_sh": ([vp, vp, vp, sz, C.POINTER(RadianceParams), i32, vp, vp, vp], C.c_int),
+            "rtx_probe_sh_device": ([vp, vp, vp, sz, C.POINTER(RadianceParams), i32, vp, vp, vp, vp], C.c_int),
+            "rtx_sh_eval": ([vp, vp, sz, i32, vp], C.c_int),
         }
         for name, (args, res) in sig.items():
             f = getattr(L, name)
@@ -649,6 +652,46 @@ class DeviceScene:
                                            C.c_void_p(stream) if stream else None), "rtx_render_mis_device")
         return n
 
+    def probe_sh(self, points, samples, max_depth, seed=1234, ids=None, first_sample=0, precision="parity",
+                 estimator=None, segments=False, backfaces=False):
+        """Light probes (rtx_probe_sh): (n, 9, 3), the radiance arriving at each point over the whole
+        sphere projected onto the real SH basis to band 2 ([coefficient][r, g, b]), from `samples`
+        paths per point in uniform directions, traced as radiance() does (estimator None), or as
+        radiance_nee() / radiance_mis() ("nee", "mis").  Sample k of probe i draws from (seed,
+        pixel = ids[i] or i, sample = first_sample + k) and equals that query of its ray
+        (probe_rays) with that id, spp = 1 and first_sample + k.  A non-finite point gives zeros.
+        segments=True: also the (n,) uint32 segments traced per probe; backfaces=True: also the
+        (n,) uint32 samples whose depth-0 segment hit a primitive from inside."""
+        points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        n = len(points)
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+            if len(ids) != n:
+                raise ValueError("probe_sh: one id per point")
+        out = np.zeros((n, 9, 3))
+        segs = np.zeros(n, np.uint32) if segments else None
+        back = np.zeros(n, np.uint32) if backfaces else None
+        p = self._radiance_params(samples, max_depth, seed, first_sample, precision)
+        _check(lib().rtx_probe_sh(self.h, points.ctypes.data_as(C.c_void_p),
+                                  None if ids is None else ids.ctypes.data_as(C.c_void_p), n, C.byref(p),
+                                  ESTIMATORS[estimator], out.ctypes.data_as(C.c_void_p),
+                                  None if segs is None else segs.ctypes.data_as(C.c_void_p),
+                                  None if back is None else back.ctypes.data_as(C.c_void_p)), "rtx_probe_sh")
+        extra = tuple(a for a in (segs, back) if a is not None)
+        return (out,) + extra if extra else out
+
+    def probe_sh_device(self, d_points, n, d_out, samples, max_depth, seed=1234, first_sample=0, precision="parity",
+                        estimator=None, d_ids=0, d_segments=0, d_backfaces=0, stream=0):
+        """The same on device buffers (rtx_probe_sh_device): d_points names n x 3 doubles, d_out
+        n x 27 doubles, d_ids n uint32 (0: the point's index), d_segments and d_backfaces n uint32
+        (0: none), e.g. torch tensors' data_ptr().  Asynchronous."""
+        p = self._radiance_params(samples, max_depth, seed, first_sample, precision)
+        _check(lib().rtx_probe_sh_device(self.h, C.c_void_p(d_points), C.c_void_p(d_ids) if d_ids else None, n,
+                                         C.byref(p), ESTIMATORS[estimator], C.c_void_p(d_out),
+                                         C.c_void_p(d_segments) if d_segments else None,
+                                         C.c_void_p(d_backfaces) if d_backfaces else None,
+                                         C.c_void_p(stream) if stream else None), "rtx_probe_sh_device")
+
     def _ao_args(self, cam, samples, radius, seed, tile, stripes, precision):
         p = RenderParams()
         p.precision = PRECISIONS[precision]
@@ -972,6 +1015,45 @@ def irradiance_rays(scene, points, normals, samples, seed, ids=None, first_sampl
     out = np.zeros((n, samples, 6))
     _check(f(scene.h, surfels.ctypes.data_as(C.c_void_p), None if ids is None else ids.ctypes.data_as(C.c_void_p), n,
              C.byref(p), out.ctypes.data_as(C.c_void_p)), "rtx_internal_irradiance_rays")
+    return out
+
+
+def probe_rays(scene, points, samples, seed, ids=None, first_sample=0):
+    """Test hook (rtx_internal_probe_rays, not in rtx.h): the depth-0 segments DeviceScene.probe_sh
+    traces for the same arguments, (n, samples, 6), from the device function the probe kernels
+    call; all zero for a point with a non-finite coordinate."""
+    points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    n = len(points)
+    if ids is not None:
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        if len(ids) != n:
+            raise ValueError("probe_rays: one id per point")
+    f = lib().rtx_internal_probe_rays
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(RadianceParams), C.c_void_p]
+    f.restype = C.c_int
+    p = DeviceScene._radiance_params(samples, 0, seed, first_sample, "parity")
+    out = np.zeros((n, samples, 6))
+    _check(f(scene.h, points.ctypes.data_as(C.c_void_p), None if ids is None else ids.ctypes.data_as(C.c_void_p), n,
+             C.byref(p), out.ctypes.data_as(C.c_void_p)), "rtx_internal_probe_rays")
+    return out
+
+
+# the constants of the real SH basis to band 2 (include/rtx.h, RTX_SH_K*)
+SH_K0, SH_K1, SH_K4 = 0.28209479177387814, 0.48860251190291992, 1.0925484305920792
+SH_K6, SH_K8 = 0.31539156525251999, 0.54627421529603959
+
+
+def sh_eval(sh, dirs, cosine=False):
+    """rtx_sh_eval: one probe's coefficients (9, 3) at unit directions (n, 3) -> (n, 3): the
+    reconstruction, or with cosine=True the cosine-convolved value over pi about each direction as
+    a normal (irradiance()'s unit).  Host only."""
+    sh = np.ascontiguousarray(sh, dtype=np.float64)
+    if sh.size != 27:
+        raise ValueError("sh_eval: 9 x 3 coefficients")
+    dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+    out = np.zeros((len(dirs), 3))
+    _check(lib().rtx_sh_eval(sh.ctypes.data_as(C.c_void_p), dirs.ctypes.data_as(C.c_void_p), len(dirs),
+                             1 if cosine else 0, out.ctypes.data_as(C.c_void_p)), "rtx_sh_eval")
     return out
 
 

@@ -5,6 +5,7 @@
 //             [--mk-adaptive MIN:THRESHOLD] [--gpus N]
 //             [--chunks N] [--preview PREFIX] [--checkpoint FILE] [--resume FILE] [--denoise]
 //             [--ao N[,RADIUS]] [--irradiance N[,DEPTH]] [--direct N] [--nee | --mis] [--adaptive] > out.ppm
+//             [--probes NX,NY,NZ[,SPP]] > probes.txt
 // --gpus N renders one frame over N GPUs (interleaved row stripes, one host thread per GPU,
 // one gathered framebuffer and P3 output; identical pixels for every N); --devices 0,2,3
 // names the devices (a device may repeat: several streams on one GPU).
@@ -42,12 +43,18 @@
 // --nee / --mis run at the same spp.  --adaptive samples every pixel until it converges (the
 // renderer's own test, 16 samples at least, threshold 0.05f) or reaches the spp.  The run logs
 // "mis film: <budget> spp, <emitters> emitters, <traced> segments traced, <recorded> recorded".
+// --probes NX,NY,NZ[,SPP] writes light probes as text instead of a PPM (rtx_probe_sh): the probes sit
+// at the cell centres of an NX x NY x NZ grid over the scene's bounding box, x fastest, keyed by
+// their index; one line per probe, "x y z" and the 27 SH coefficients ([coefficient][r, g, b]), each
+// number with %.17g.  SPP samples per probe (default 256); depth and seed are the preset's (or
+// --depth, --seed), --precision applies, --nee / --mis choose the estimator.
 // --mk-adaptive selects the AdaptiveSampler (sampler.h:44-82) for --mode megakernel,
 // with max_samples = the preset's (or --spp) samples.
 // Defaults follow main.cc: preset "default" (fallback when unknown), the Cornell box
 // scene (switch(4), main.cc:178-183), WavefrontRenderer with the preset's maxDepth and
 // samplesPerPixel, adaptive sampling on; "Runtime: Xs" on stderr.
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -74,6 +81,8 @@ int main(int argc, char** argv) {
   bool irr = false;
   int direct_samples = 0;  // --direct
   bool direct = false;
+  int probes[4] = {0, 0, 0, 256};  // --probes NX,NY,NZ[,SPP]
+  bool probe = false;
   bool nee = false;  // --nee
   bool mis = false;  // --mis
   double ao_radius = 0.0;  // 0: a quarter of the scene's bounding-box diagonal
@@ -129,6 +138,26 @@ int main(int argc, char** argv) {
       direct_samples = std::atoi(next().c_str());
       if (direct_samples < 1) {
         std::cerr << "--direct expects N >= 1\n";
+        return 2;
+      }
+    }
+    else if (a == "--probes") {
+      const std::string v = next();
+      probe = true;
+      int fields = 0;
+      bool ok = !v.empty();
+      for (size_t p = 0; ok && p <= v.size();) {
+        size_t q = v.find(',', p);
+        if (q == std::string::npos) q = v.size();
+        const std::string f = v.substr(p, q - p);
+        char* end = nullptr;
+        const long val = std::strtol(f.c_str(), &end, 10);
+        ok = fields < 4 && !f.empty() && *end == '\0' && val >= 1 && val <= 0x7FFFFFFF;
+        if (ok) probes[fields++] = (int)val;
+        p = q + 1;
+      }
+      if (!ok || fields < 3 || (int64_t)probes[0] * probes[1] * probes[2] > ((int64_t)1 << 24)) {
+        std::cerr << "--probes expects NX,NY,NZ[,SPP], each >= 1, at most 2^24 probes\n";
         return 2;
       }
     }
@@ -196,7 +225,38 @@ int main(int argc, char** argv) {
       std::cerr << "--denoise needs --mode wavefront or persistent\n";
       return 2;
     }
-    if (ao_samples > 0) {
+    if (probe) {
+      integrator::GpuRayIntegrator integ(world.get(), devices.empty() ? 0 : devices[0],
+                                         precision == "fast" ? RTX_PREC_FAST : RTX_PREC_PARITY);
+      const geom::Aabb b = world->BoundingBox();
+      const double lo[3] = {b.x.min_, b.y.min_, b.z.min_}, hi[3] = {b.x.max_, b.y.max_, b.z.max_};
+      std::vector<core::Point3> pts;
+      for (int iz = 0; iz < probes[2]; iz++)
+        for (int iy = 0; iy < probes[1]; iy++)
+          for (int ix = 0; ix < probes[0]; ix++) {
+            const int at[3] = {ix, iy, iz};
+            double c[3];
+            for (int k = 0; k < 3; k++) c[k] = lo[k] + (hi[k] - lo[k]) * (((double)at[k] + 0.5) / (double)probes[k]);
+            pts.push_back(core::Point3(c[0], c[1], c[2]));
+          }
+      std::vector<double> sh;
+      integ.ProbeBatch(pts, sh, probes[3], md, seed, mis ? RTX_ESTIMATOR_MIS : (nee ? RTX_ESTIMATOR_NEE : 0));
+      std::string out;
+      char num[40];
+      for (size_t i = 0; i < pts.size(); i++) {
+        for (int k = 0; k < 3; k++) {
+          std::snprintf(num, sizeof num, k ? " %.17g" : "%.17g", pts[i][k]);
+          out += num;
+        }
+        for (int q = 0; q < 3 * RTX_SH_COEFFS; q++) {
+          std::snprintf(num, sizeof num, " %.17g", sh[3 * RTX_SH_COEFFS * i + q]);
+          out += num;
+        }
+        out += "\n";
+      }
+      std::cout.write(out.data(), (std::streamsize)out.size());
+      std::clog << "probes: " << pts.size() << " probes, " << probes[3] << " samples, depth " << md << "\n";
+    } else if (ao_samples > 0) {
       integrator::GpuRayIntegrator integ(world.get(), devices.empty() ? 0 : devices[0],
                                          precision == "fast" ? RTX_PREC_FAST : RTX_PREC_PARITY);
       if (!(ao_radius > 0)) {

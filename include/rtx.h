@@ -708,6 +708,62 @@ int rtx_render_mis(rtx_scene* scene, const rtx_camera* cam, const rtx_render_par
 int rtx_render_mis_device(rtx_scene* scene, const rtx_camera* cam, const rtx_render_params* params,
                           double* d_out_rgb, uint32_t* d_out_segments, void* stream);
 
+/* ---- light probes (DESIGN.md "Light probes") --------------------------------------------------
+ * How much light arrives at these points from every direction?  The radiance over the whole sphere
+ * about a point that need lie on no surface, projected onto real spherical harmonics to band 2:
+ * nine coefficients per colour channel, for lighting moving objects and volumes.  No ray and no
+ * per-sample value goes through caller memory.  A probe is three doubles.  rtx_radiance_params is
+ * read as by rtx_radiance, spp being the samples per probe.  estimator: 0 (the plain path),
+ * RTX_ESTIMATOR_NEE or RTX_ESTIMATOR_MIS.  For probe i and sample k in [0, spp):
+ *   direction: two numbers u1, u2 from a Philox stream of its own (0xA4000000) keyed by (seed,
+ *     pixel = ids ? ids[i] : (uint32_t)i, sample = first_sample + k) give z = 1 - 2 u1,
+ *     phi = 2 pi u2, r = sqrt(max(0, 1 - z z)), d = (r cos phi, r sin phi, z): uniform over the
+ *     sphere, |d| = 1 to rounding;
+ *   path: the ray (point, d) is the depth-0 segment of a path with throughput 1.  With estimator 0
+ *     its value L_k is, bit for bit, rtx_radiance of that one ray with the same id, spp = 1 and
+ *     first_sample = first_sample + k; with RTX_ESTIMATOR_NEE / _MIS rtx_radiance_nee /
+ *     rtx_radiance_mis of it, and its segment count likewise.  The probe is no vertex: an emitter
+ *     seen directly at depth 0 counts in full, as for a camera ray.
+ *   basis: with (x, y, z) = d, in this order and with these operations (no contraction):
+ *     Y0 = K0, Y1 = K1*y, Y2 = K1*z, Y3 = K1*x, Y4 = K4*(x*y), Y5 = K4*(y*z),
+ *     Y6 = K6*(3.0*(z*z) - 1.0), Y7 = K4*(x*z), Y8 = K8*(x*x - y*y),
+ *     the constants below: the closed forms rounded to the nearest double.
+ * out_sh: 27 doubles per probe, [coefficient j][r, g, b]: the products Y_j(d_k) * L_k[c] added in
+ * sample order from 0, resolved as (4 pi) * ((1 / (double)(float)spp) * sum): the Monte-Carlo
+ * estimate of the integral of L(w) Y_j(w) over the sphere.
+ * out_segments (may be NULL): as rtx_irradiance's, all segments of the probe's samples.
+ * out_backfaces (may be NULL): the samples whose depth-0 segment hit a primitive from inside
+ * (front_face == 0 in the hit record): a probe buried in geometry reports spp, one in the open 0.
+ * A probe with a non-finite coordinate traces nothing: 27 zeros and two zero counts, decided on the
+ * device.  Checks: rtx_radiance's in its order and with its messages (scene, params, buffers: points
+ * and out_sh, spp, first_sample, max_depth, precision), then the estimator ("probe: bad
+ * estimator"), then for RTX_ESTIMATOR_NEE / _MIS the max_depth cap of rtx_radiance_nee /
+ * rtx_radiance_mis; then n == 0 returns RTX_OK.  The live scene is read (after rtx_scene_update_*
+ * the new geometry).  One call at a time per scene. */
+#define RTX_SH_COEFFS 9
+#define RTX_SH_K0 0.28209479177387814 /* 1 / (2 sqrt(pi)) */
+#define RTX_SH_K1 0.48860251190291992 /* sqrt(3 / (4 pi)) */
+#define RTX_SH_K4 1.0925484305920792  /* sqrt(15 / (4 pi)) */
+#define RTX_SH_K6 0.31539156525251999 /* sqrt(5 / (16 pi)) */
+#define RTX_SH_K8 0.54627421529603959 /* sqrt(15 / (16 pi)) */
+/* Host buffers, staged through pinned memory in batches; returns when the outputs are written. */
+int rtx_probe_sh(rtx_scene* scene, const double* points, const uint32_t* ids, size_t n,
+                 const rtx_radiance_params* params, int32_t estimator, double* out_sh, uint32_t* out_segments,
+                 uint32_t* out_backfaces);
+/* Device buffers; asynchronous on stream (NULL = the scene's stream). */
+int rtx_probe_sh_device(rtx_scene* scene, const double* d_points, const uint32_t* d_ids, size_t n,
+                        const rtx_radiance_params* params, int32_t estimator, double* d_out_sh,
+                        uint32_t* d_out_segments, uint32_t* d_out_backfaces, void* stream);
+/* The coefficients of one probe (27 doubles, rtx_probe_sh's layout) evaluated at n unit directions
+ * (3 doubles each; not normalised here), 3 doubles out per direction, the basis formed as above.
+ * cosine == 0: the reconstruction, per channel ((..(c_0 Y_0 + c_1 Y_1) + ..) + c_8 Y_8).
+ * cosine == 1: the cosine-convolved value over pi, with `dir` the surface normal:
+ * c_0 Y_0 + (2/3) (c_1 Y_1 + c_2 Y_2 + c_3 Y_3) + (1/4) (c_4 Y_4 + .. + c_8 Y_8), each bracket added
+ * left to right, the factors 2.0 / 3.0 and 0.25: rtx_irradiance's unit, so the two compare.
+ * Host only, plain C++: NULL buffers with n > 0 or sh NULL ("NULL buffer") and cosine outside 0..1
+ * ("sh eval: cosine must be 0 or 1") are RTX_ERR_INVALID; no device is touched. */
+int rtx_sh_eval(const double* sh, const double* dirs, size_t n, int32_t cosine, double* out_rgb);
+
 enum { RTX_DENOISE_DEMODULATE = 1 }; /* filter colour / max(albedo, 1e-3), multiply back at the end */
 typedef struct {
   int32_t iterations; /* 0..8; iteration k filters 5 x 5 taps at step 2^k; 0 copies the input */
